@@ -3,7 +3,10 @@
 
   "samples/sec whole-node ResNet-50 DP + GPT-2 PP at 1/2/4/8 MI355X; scaling eff"
 
-Default (the driver's contract) measures BOTH halves of the metric in one run:
+A plain run (the driver's contract) measures the headline only: it sets up, warms up, times the K
+steps of the primary ``value``, writes that path's outputs (``--dump-outputs DIR``) and prints the
+result line.  ``--full`` measures BOTH halves of the metric in one run, and the standard-batch
+ResNet-50 figure next to the primary one:
 
 * the primary ``value``: ResNet-50, automatic data parallelism
   (``madnn.distribute``), bf16 compute with fp32 master weights and fp32 BatchNorm,
@@ -12,7 +15,7 @@ Default (the driver's contract) measures BOTH halves of the metric in one run:
   of the 288 GB HBM; same-box A/Bs: 10.80k img/s at 512 vs 11.37k at 1024,
   profiles/r2_resnet_b1024.md; 11.38k at 1024 vs 11.59k at 1536, profiles/r2_resnet_b1536.md;
   12.65k at 1536 vs 12.85k at 2048, profiles/r2_resnet_b2048.md);
-* ``gpt2_pp``: GPT-2 medium (seq 1024, bf16, FusedAdam), pipeline parallel over
+* ``gpt2_pp`` (``--full``): GPT-2 medium (seq 1024, bf16, FusedAdam), pipeline parallel over
   RCCL P2P -- ``pp2`` at 2 GPUs, ``pp4`` at 4, ``dp2 x pp4`` at 8; data parallel at 1 GPU
   (a pipeline needs two stages); 128 sequences per GPU (weak scaling).  The schedule (GPipe,
   1F1B, interleaved with 2 or 4 chunks per rank) and the microbatch count are the planner's
@@ -22,17 +25,22 @@ Default (the driver's contract) measures BOTH halves of the metric in one run:
   sequences: 194k / 235k / 277k / 308k / 326k tok/s) against the simulated bubble.
   ``--schedule`` / ``--microbatches`` / ``--gpt2-mb`` pin them by hand.
 
-Synthetic data and random init (no network on the box).  ``--model resnet50`` /
-``--model gpt2-medium`` run one half only.  Without a launcher environment the
+Synthetic data and random init (no network on the box), seeded: the same arguments give the same
+inputs in every run.  ``--model resnet50`` / ``--model gpt2-medium`` run one half only (with
+``--full`` too).  Without a launcher environment the
 process still joins a world-1 RCCL group (``--no-pg`` disables it), so the 1-GPU
 number is taken on the same communicator / reducer path as the 8-GPU one.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
 Times exactly K steps between a barrier + device synchronize on both sides,
 takes the MAX over ranks, and rank 0 prints ONE JSON line.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the timed path returned in its
+last step as ``DIR/<name>.npy`` (float32): ResNet-50's logits and loss (they carry the forward,
+backward and optimizer kernels of every earlier step), the loss of a transformer's ``train_step``.
 """
 from __future__ import annotations
 
@@ -59,9 +67,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything the record can hold, not only the headline: with --model all the GPT-2 "
+                         "half (gpt2_pp) too, and ResNet-50 again at --std-batch")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the timed path returned in its last step as "
+                         "DIR/<name>.npy (float32)")
     ap.add_argument("--model", default="all", choices=["all", "resnet50", "gpt2-medium", "bert-large", "llama3-8b"],
-                    help="all (the driver's contract: ResNet-50 + GPT-2), one half of it, or one of BASELINE's other "
-                         "configs: bert-large (config 5) / llama3-8b (config 4), planned by madnn.distribute "
+                    help="all (the driver's contract: ResNet-50, and with --full GPT-2), one half of it, or one of "
+                         "BASELINE's other configs: bert-large (config 5) / llama3-8b (config 4), planned by madnn.distribute "
                          "(strategy and activation checkpointing are the planner's)")
     ap.add_argument("--tf-config", default=None,
                     help="bert / llama size for --model bert-large|llama3-8b (default: that model; bert-tiny / "
@@ -104,7 +118,7 @@ def parse():
                          "lets tests run several ranks on one GPU, which RCCL refuses")
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--std-batch", type=int, default=512,
-                    help="also time ResNet-50 at this standard per-GPU batch (config.std_batch; 0 = skip)")
+                    help="--full: also time ResNet-50 at this standard per-GPU batch (config.std_batch; 0 = skip)")
     ap.add_argument("--gpt2-timeout", type=float, default=420.0,
                     help="seconds the GPT-2 phase may take before it is reported as an error (below the 600 s "
                          "process-group timeout, whose watchdog would abort the process first)")
@@ -165,11 +179,14 @@ def bench_resnet(args, world, rank):
                                       torch.float32, channels_last=bool(args.channels_last), seed=1234 + rank,
                                       shape=(3, args.image_size, args.image_size))
 
+    last = {}
+
     def step():
         out = dmodel(x)
         loss = F.cross_entropy(out.float(), y)
         loss.backward()
         opt.step()
+        last["logits"] = out   # what the caller of the step holds (--dump-outputs); a reference, no copy
         return loss
 
     tw = time.perf_counter()
@@ -190,6 +207,8 @@ def bench_resnet(args, world, rank):
         loss = run()
     _sync_all()
     dt = time.perf_counter() - t0
+    _keep(args, "resnet50_logits", last["logits"])
+    _keep(args, "resnet50_loss", loss)
     if run is not step:
         step()   # one eager step after the timed region: its comm events feed comm_metrics
         _sync_all()
@@ -345,6 +364,7 @@ def bench_gpt2(args, world, rank):
             "loss_last_stage": lv, "heldout_loss": held, "ln_vocab": round(math.log(cfg.vocab_size), 4),
             "accum_microbatches": args.microbatches if stages == 1 and args.microbatches else None,
             "peak_mem_gib": _peak_gib(), "plan": _plan_info(plan), **_comm_fields(engine, plan)}
+    _keep(args, "gpt2_loss", lv)
     return dt, steps, gbatch, info
 
 
@@ -434,6 +454,7 @@ def bench_transformer(args, world, rank):
     _sync_all()
     dt = _max_over_ranks(time.perf_counter() - t0)
     lv = float(loss.detach()) if loss is not None else None
+    _keep(args, name.replace("-", "_") + "_loss", loss)
     held = _heldout_loss(engine, model, cfg.vocab_size, ids.shape, 98765 + replica, stages, rank)
     ck = sum(bool(c) for c in plan.checkpoint) if plan is not None and plan.checkpoint else 0
     nl = len(plan.checkpoint) if plan is not None and plan.checkpoint else None
@@ -592,7 +613,7 @@ def main():
         }
         config["per_gpu_value"] = float(f"{res['value'] / world:.6g}")
         _release()
-        if args.std_batch and args.std_batch != config["per_gpu_batch"]:
+        if args.full and args.std_batch and args.std_batch != config["per_gpu_batch"]:
             # the same measurement at a standard per-GPU batch, so rounds compare like for like
             sargs = argparse.Namespace(**dict(vars(args), batch=args.std_batch))
             sdt, sps_step, sconf = bench_resnet(sargs, world, rank)
@@ -604,7 +625,7 @@ def main():
                                           "warmup_s": sconf["warmup_s"], "parallelism": sconf["parallelism"],
                                           **{k: sconf.get(k) for k in ("comm_exposed_ms", "busbw_gbps", "p2p_gbps")}}
             _release()
-    if args.model in ("all", "gpt2-medium"):
+    if args.model == "gpt2-medium" or (args.model == "all" and args.full):
         if args.model == "all":
             import gc
 
@@ -636,7 +657,37 @@ def main():
 _RANKS: dict = {}   # ranks_seen / devices of this job (_check_ranks), added to every record
 
 
+_DUMP: dict = {}    # name -> host array of the timed path's last step (--dump-outputs)
+DUMP_BYTES = 64 * 10**6   # all of --dump-outputs together stays below this
+
+
+def _keep(args, name, value):
+    """Remember one output of the timed path's last step for ``--dump-outputs`` (called after the
+    timed region; the first value under a name stays, so the standard-batch rerun does not
+    replace the headline's)."""
+    if args.dump_outputs and value is not None and name not in _DUMP:
+        t = value.detach() if torch.is_tensor(value) else torch.tensor(value, dtype=torch.float64)
+        _DUMP[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+
+
+def _dump_outputs(args, rank):
+    """Rank 0 writes ``DIR/<name>.npy``; an array over its share of DUMP_BYTES is cut to a fixed
+    (seed 0) sorted sample of its flattened elements."""
+    if not args.dump_outputs or rank != 0:
+        return
+    import numpy as np
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BYTES // max(len(_DUMP), 1)
+    for name, a in _DUMP.items():
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+
 def _emit(res, rank, args):
+    _dump_outputs(args, rank)
     if rank == 0:
         line = json.dumps(dict(res, **_RANKS))
         print(line, flush=True)

@@ -4,7 +4,7 @@ set -u
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/bench_all
 mkdir -p $O
-timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 > $O/gpt2.log 2>&1 || { tail -20 $O/gpt2.log; exit 3; }
+timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 > $O/gpt2.log 2>&1 || { tail -20 $O/gpt2.log; exit 3; }
 tail -1 $O/gpt2.log
 timeout -k 10 400 python -u bench.py --model bert-large --steps 10 --warmup 3 > $O/bert.log 2>&1 || { tail -20 $O/bert.log; exit 3; }
 tail -1 $O/bert.log

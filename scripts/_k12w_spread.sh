@@ -9,7 +9,7 @@ timeout -k 10 300 python -u bench/gemm_wgrad_ab.py --out $O/ab.json > $O/ab.log 
 timeout -k 10 900 python -u scripts/record_tuning.py --out $O/tuning --keep-table --retime wgrad:linear,wgrad:conv1x1 > $O/tuning.log 2>&1
 tail -n 1 $O/tuning.log
 cp $O/tuning/choices_gfx950.json madnn/tuning/choices_gfx950.json
-timeout -k 10 600 python -u bench.py > $O/bench_default.json 2> $O/bench_default.log
+timeout -k 10 600 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.log
 python - <<'PY'
 import json, collections
 r=json.loads(open("gpurun_out/k12wh/bench_default.json").read().strip().splitlines()[-1])

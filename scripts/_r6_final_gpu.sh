@@ -9,7 +9,7 @@ tail -n 3 $O/gpu_tests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 3; }
 tail -n 1 $O/smoke.log
-timeout -k 10 600 python -u bench.py > $O/bench_default.json 2> $O/bench_default.log || { tail -20 $O/bench_default.log; exit 4; }
+timeout -k 10 600 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.log || { tail -20 $O/bench_default.log; exit 4; }
 python - <<'PY'
 import json
 r=json.loads(open("gpurun_out/r6f/bench_default.json").read().strip().splitlines()[-1])

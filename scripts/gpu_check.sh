@@ -25,7 +25,7 @@ for s in $STAGES; do
     tests) stage tests 900 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread ;;
     ktests) stage ktests 600 python -m pytest tests/test_kernels_gpu.py -q ;;
     smoke) stage smoke 400 python __graft_entry__.py smoke ;;
-    bench) stage bench 600 python bench.py --steps 30 --warmup 10 ;;
+    bench) stage bench 600 python bench.py --full --steps 30 --warmup 10 ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
           -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --steps 10 --warmup 5 > "$OUT/prof.log" 2>&1)

@@ -46,7 +46,7 @@ def test_bench_gpt2_medium_pp2_on_device(cuda):
 
 def _run_rccl_world1(cmd_head, extra):
     cmd = cmd_head + ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "32",
-                      "--image-size", "64", "--gpt2-batch-per-gpu", "2", "--seq-len", "128"] + extra
+                      "--image-size", "64", "--gpt2-batch-per-gpu", "2", "--seq-len", "128", "--full"] + extra
     env = dict(os.environ, MADNN_LOG_LEVEL="WARNING", OMP_NUM_THREADS="4")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -60,6 +60,26 @@ def _run_rccl_world1(cmd_head, extra):
     assert res["config"]["parallelism"] == "dp1" and res["value"] > 0
     assert res["gpt2_pp"]["parallelism"] == "dp1" and res["gpt2_pp"]["tokens_per_s"] > 0
     return res
+
+
+def test_bench_plain_run_dumps_outputs_on_device(cuda, tmp_path):
+    """The plain 1-GPU command measures the headline only and ``--dump-outputs`` writes the last
+    timed step's bf16 logits and fp32 loss as float32 arrays."""
+    import numpy as np
+
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "32",
+           "--image-size", "64", "--dump-outputs", str(tmp_path)]
+    env = dict(os.environ, MADNN_LOG_LEVEL="WARNING", OMP_NUM_THREADS="4")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert "gpt2_pp" not in res and "std_batch" not in res["config"]
+    assert res["steps"] == 2 and res["dtype"] == "bf16" and res["ms_per_step"] > 0
+    logits, loss = np.load(tmp_path / "resnet50_logits.npy"), np.load(tmp_path / "resnet50_loss.npy")
+    assert logits.dtype == np.float32 and logits.shape == (32, 1000) and np.isfinite(logits).all()
+    assert float(loss) == pytest.approx(res["config"]["loss"], rel=1e-6)
 
 
 def test_bench_rccl_world1_under_torchrun(cuda):

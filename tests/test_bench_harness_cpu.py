@@ -20,7 +20,7 @@ def test_bench_py_two_ranks_cpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--device", "cpu", "--batch", "2", "--image-size", "32", "--gpt2-config", "gpt2-tiny", "--seq-len", "32",
-           "--gpt2-batch-per-gpu", "4", "--gpt2-mb", "2"]
+           "--gpt2-batch-per-gpu", "4", "--gpt2-mb", "2", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="2", MADNN_LOG_LEVEL="WARNING")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -56,7 +56,8 @@ def test_bench_py_two_ranks_cpu():
 def test_bench_py_single_process_joins_world1_group():
     """No launcher: bench.py still creates a world-1 process group (gloo here, RCCL on the GPU)."""
     cmd = [sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--device", "cpu", "--batch", "2",
-           "--image-size", "32", "--gpt2-config", "gpt2-tiny", "--seq-len", "16", "--gpt2-batch-per-gpu", "2"]
+           "--image-size", "32", "--gpt2-config", "gpt2-tiny", "--seq-len", "16", "--gpt2-batch-per-gpu", "2",
+           "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(OMP_NUM_THREADS="2", MADNN_LOG_LEVEL="WARNING")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
@@ -65,6 +66,36 @@ def test_bench_py_single_process_joins_world1_group():
     assert res["n_gpus"] == 1 and res["config"]["process_group"] == "gloo"
     assert res["config"]["parallelism"] == "dp1" and res["gpt2_pp"]["parallelism"] == "dp1"
     assert res["ranks_seen"] == 1 and res["devices"] == ["cpu"]
+
+
+def test_bench_py_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the run measures the headline alone (no GPT-2 half, no standard-batch
+    rerun), times exactly ``--steps`` steps, and ``--dump-outputs`` writes the last timed step's
+    logits and loss as float32 ``.npy``; a second run with the same arguments has the same inputs,
+    so on CPU it writes the same arrays."""
+    import numpy as np
+
+    def run(out_dir):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--device", "cpu",
+               "--batch", "2", "--image-size", "32", "--dump-outputs", str(out_dir)]
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=_no_launcher_env())
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        return json.loads(lines[0])
+
+    res = run(tmp_path / "a")
+    assert "gpt2_pp" not in res and "std_batch" not in res["config"]
+    assert res["steps"] == 2 and res["warmup"] == 1 and res["unit"] == "samples/s" and res["higher_is_better"] is True
+    # value = samples / time of the 2 timed steps (the record rounds it to 0.01 samples/s)
+    assert res["value"] == pytest.approx(2 * 2 / (res["ms_per_step"] * 2 / 1000), rel=1e-3, abs=0.006)
+    assert sorted(os.listdir(tmp_path / "a")) == ["resnet50_logits.npy", "resnet50_loss.npy"]
+    logits, loss = np.load(tmp_path / "a" / "resnet50_logits.npy"), np.load(tmp_path / "a" / "resnet50_loss.npy")
+    assert logits.dtype == np.float32 and logits.shape == (2, 1000) and np.isfinite(logits).all()
+    assert loss.dtype == np.float32 and float(loss) == pytest.approx(res["config"]["loss"], rel=1e-6)
+    run(tmp_path / "b")
+    # same seeds, same inputs; fp32 sums may be ordered differently between two processes
+    np.testing.assert_allclose(np.load(tmp_path / "b" / "resnet50_logits.npy"), logits, rtol=1e-4, atol=1e-5)
 
 
 def _no_launcher_env(**extra):
@@ -204,7 +235,7 @@ def test_bench_py_reports_resnet_when_gpt2_phase_fails():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1",
            "--device", "cpu", "--batch", "4", "--std-batch", "2", "--image-size", "32", "--gpt2-config", "gpt2-tiny",
-           "--seq-len", "16", "--gpt2-batch-per-gpu", "2", "--gpt2-mb", "1", "--gpt2-timeout", "60"]
+           "--seq-len", "16", "--gpt2-batch-per-gpu", "2", "--gpt2-mb", "1", "--gpt2-timeout", "60", "--full"]
     for fault in ("1:1:raise", "1:1:hang"):
         env = dict(os.environ, OMP_NUM_THREADS="2", MADNN_LOG_LEVEL="WARNING", MADNN_BENCH_GPT2_FAULT=fault)
         out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
