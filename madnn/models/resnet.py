@@ -27,8 +27,8 @@ from torch import nn
 from ..nn.conv import FusedConv2d
 from ..nn.norm import FusedBatchNorm2d as BN
 from ..nn.norm import FusedGlobalAvgPool2d, FusedMaxPool2d
-from ..ops import (batch_norm_add_bn_relu, bn_relu_conv1x1, bn_relu_conv1x1_epi_supported,
-                   bn_relu_conv3x3, conv1x1_route,
+from ..ops import (batch_norm_add_bn_relu, bn2_conv3_bn3_add_relu, bn2_conv3_bn3_supported, bn_relu_conv1x1,
+                   bn_relu_conv1x1_epi_supported, bn_relu_conv3x3, conv1x1_route,
                    bn_relu_conv3x3_supported, bn_relu_maxpool, bn_relu_maxpool_supported)
 
 # A/B knob: sum the downsample path's input gradient inside conv1's data grad (1) or by autograd (0)
@@ -112,6 +112,11 @@ class Bottleneck(nn.Module):
             idt = self.downsample(x)
             y, st = self.conv1(x, stats=True)
         y, st = self._bn1_conv2(y, st)   # K13 at stride 1: BN statistics from the epilogue
+        if self.downsample is None and isinstance(self.bn2, BN) and isinstance(self.bn3, BN) \
+                and isinstance(self.conv3, FusedConv2d) and isinstance(y, torch.Tensor) and self.conv3._k9(y) \
+                and bn2_conv3_bn3_supported(y, self.bn2, self.conv3.weight, self.bn3, idt):
+            # layer 1's identity blocks: one backward kernel for bn3's apply and conv3's two gradients (K9F)
+            return bn2_conv3_bn3_add_relu(y, self.bn2, self.conv3.weight, self.bn3, idt, stats_in=st)
         y, st = self._bn2_conv3(y, st)
         return self.bn3(y, residual=idt, relu=True, stats=st)   # relu(bn3 + idt): one kernel
 

@@ -907,6 +907,74 @@ def bn_relu_conv1x1_epi_supported(y: torch.Tensor, bn, w: torch.Tensor) -> bool:
             and conv1x1_route(y.size(1), w.size(0))[1] == "k9")
 
 
+class _BN2Conv3BN3Fn(torch.autograd.Function):
+    """``relu(bn3(conv3(relu(bn2(y2)))) + idt)`` in training, the tail of a ResNet identity bottleneck
+    (K9F).  Forward: the kernels of :class:`_BNReluConv1x1EpiFn` and :class:`_BNFn`, unchanged.
+    Backward: bn3's reduction + finalize, then one kernel that forms ``dy3`` in registers and feeds
+    conv3's data grad (with bn2's backward sums) and weight grad from it -- ``dy3`` is never written
+    -- then bn2's finalize + apply.  ``idt``'s gradient is ``dout`` with bn3's ReLU bit mask attached
+    (the deferred residual mask of :class:`_BNFn`)."""
+
+    @staticmethod
+    def forward(ctx, y2, w3, bn2_w, bn2_b, bn3_w, bn3_b, idt, bn2, bn3, stats_in):
+        a2, mean2, invstd2, scale2, shift2, _ = torch.ops.madnn.bn_fwd(
+            y2, None, bn2_w, bn2_b, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked, True,
+            float(bn2.momentum), float(bn2.eps), True, stats_in)
+        y3, part = torch.ops.madnn.conv1x1_fwd(a2, w3, True)
+        out, mean3, invstd3, scale3, shift3, mask = torch.ops.madnn.bn_fwd(
+            y3, idt, bn3_w, bn3_b, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked, True,
+            float(bn3.momentum), float(bn3.eps), True, part)
+        ctx.save_for_backward(y2, a2, w3, y3, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3, invstd3,
+                              scale3, shift3)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (y2, a2, w3, y3, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3, invstd3, scale3,
+         shift3) = ctx.saved_tensors
+        if dout.dtype != y3.dtype or dout.stride() != y3.stride():
+            dout = torch.empty_like(y3).copy_(dout)
+        coef, dbw3, dbb3 = torch.ops.madnn.bn_bwd_coef(dout, y3, mask, bn3_w, mean3, invstd3, scale3, shift3)
+        da2, part, dw3 = torch.ops.madnn.bn3_conv3_bwd(dout, y3, mask, coef, w3, a2, y2, scale2, shift2,
+                                                       w3.dtype == torch.bfloat16)
+        dy2, dbw2, dbb2 = torch.ops.madnn.bn_bwd_ext(da2, y2, bn2_w, mean2, invstd2, scale2, shift2, part, True)
+        dres = dout.view_as(dout)
+        _attach(dres, "_madnn_resmask", mask)
+        need2 = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        need3 = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        return (dy2, dw3.to(w3.dtype).view(w3.shape), dbw2 if need2 else None, dbb2 if need2 else None,
+                dbw3 if need3 else None, dbb3 if need3 else None, dres, None, None, None)
+
+
+_BN3_CONV3_FUSED = os.environ.get("MADNN_BN3_CONV3_FUSED", "1") != "0"  # A/B switch (K9F)
+
+
+def bn2_conv3_bn3_supported(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, idt: torch.Tensor) -> bool:
+    """Inputs :func:`bn2_conv3_bn3_add_relu` runs with the fused backward kernel: the layer-1 identity
+    bottleneck shape (64 -> 256 channels), both BatchNorms training with fp32 affine parameters, conv3's
+    forward and data grad on K9, and an identity whose ReLU mask is deferred to its consumer."""
+    def ok(m):
+        return (m.training and m.track_running_stats and m.affine and m.momentum is not None
+                and m.weight.dtype == torch.float32)
+    if not (_BN3_CONV3_FUSED and DEFER_RES_MASK and isinstance(y2, torch.Tensor) and isinstance(idt, torch.Tensor)):
+        return False
+    c, c4 = y2.size(1), w3.size(0)
+    return (bn_relu_conv1x1_epi_supported(y2, bn2, w3) and native_available()
+            and bool(torch.ops.madnn.bn3_conv3_bwd_supported(c, c4)) and conv1x1_route(c, c4)[0] == "k9" and ok(bn2) and ok(bn3)
+            and bn3.weight.numel() == c4 and y2.requires_grad and torch.is_grad_enabled()
+            and getattr(idt, "_madnn_defer_mask", False) and idt.dtype == y2.dtype and idt.dim() == y2.dim()
+            and idt.size(1) == c4 and idt.shape[2:] == y2.shape[2:] and idt.size(0) == y2.size(0)
+            and bn_supported(idt, bn3.weight))
+
+
+def bn2_conv3_bn3_add_relu(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, idt: torch.Tensor,
+                           stats_in: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``relu(bn3(conv1x1(relu(bn2(y2)), w3)) + idt)`` (see :class:`_BN2Conv3BN3Fn`); the caller checks
+    :func:`bn2_conv3_bn3_supported`."""
+    _need_native("bn2_conv3_bn3_add_relu")
+    return _BN2Conv3BN3Fn.apply(y2, w3, bn2.weight, bn2.bias, bn3.weight, bn3.bias, idt, bn2, bn3, stats_in)
+
+
 class _BNReluMaxPoolFn(torch.autograd.Function):
     """``max_pool2d(relu(bn(y)), 3, 2, 1)`` in training (ResNet's stem): the BN apply + ReLU run
     inside the pool's window loads; backward gathers the pool gradient per input pixel inside the
@@ -1219,7 +1287,7 @@ __all__ = [
     "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
     "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
     "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",
-    "bn_relu_conv1x1_epi_supported", "conv1x1_supported", "stem_conv", "stem_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
+    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "conv1x1_supported", "stem_conv", "stem_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
 ]
 
 if os.environ.get("MADNN_EAGER_LOAD", "0") == "1":

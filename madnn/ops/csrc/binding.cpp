@@ -77,6 +77,14 @@ hipError_t madnn_bn_fwd_dual(const void*, const void*, void*, unsigned char*, in
 hipError_t madnn_bn_bwd_dual(const void*, const void*, const void*, const unsigned char*, void*, void*, int64_t, int,
                              const float*, const float*, const float*, const float*, const float*, const float*,
                              float*, float*, float*, float*, float*, float*, hipStream_t);
+hipError_t madnn_bn_bwd_coef(const void*, const void*, const unsigned char*, int, int64_t, int, int, int, const float*,
+                             const float*, const float*, const float*, const float*, float*, float*, float*, float*,
+                             hipStream_t);
+int madnn_bn3_conv3_bwd_supported(int64_t, int64_t);
+int madnn_bn3_conv3_bwd_groups(int64_t);
+hipError_t madnn_bn3_conv3_bwd(const void*, const void*, const unsigned char*, const float*, const void*, const void*,
+                               const void*, const float*, const float*, void*, float*, float*, void*, int, int64_t,
+                               int64_t, int64_t, hipStream_t);
 int madnn_conv1x1_supported(int64_t, int64_t);
 int madnn_conv1x1_stat_rows(int64_t, int64_t, int64_t);
 hipError_t madnn_conv1x1_fwd(const void*, const void*, void*, float*, int64_t, int64_t, int64_t, hipStream_t);
@@ -676,6 +684,69 @@ at::Tensor conv1x1_wgrad(const at::Tensor& dy, const at::Tensor& x, bool out_bf1
                             cout, cur_stream(x)),
         "conv1x1_wgrad");
   return dw;
+}
+
+// bn(+ residual)+ReLU backward without the apply pass: the reduction over (dy, x, ReLU bit mask) and the
+// finalize -> (coef [3, C] = ca | cb | cc of dx = ca g + cb x + cc, dw, db)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_bwd_coef(const at::Tensor& dy, const at::Tensor& x,
+                                                           const at::Tensor& mask, const c10::optional<at::Tensor>& w,
+                                                           const at::Tensor& save_mean, const at::Tensor& save_invstd,
+                                                           const at::Tensor& scale, const at::Tensor& shift) {
+  check_dev(x, "x");
+  const int64_t C = x.size(1);
+  const int64_t M = bn_rows(x, C);
+  TORCH_CHECK(dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type(), "bn_bwd_coef: dy / x of one layout");
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() == x.numel() / 8,
+              "bn_bwd_coef: ReLU bit mask required");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto fo = x.options().dtype(at::kFloat);
+  at::Tensor dw = at::empty({C}, fo), db = at::empty({C}, fo), coef = at::empty({3, C}, fo);
+  at::Tensor ws = at::empty({(int64_t)madnn_bn_partial_rows(M, (int)C) * 2 * C}, fo);
+  check(madnn_bn_bwd_coef(dy.data_ptr(), x.data_ptr(), mask.data_ptr<uint8_t>(), 1, M, (int)C, dt_code(x), 1, optf(w),
+                          save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), scale.data_ptr<float>(),
+                          shift.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(), coef.data_ptr<float>(),
+                          ws.data_ptr<float>(), cur_stream(x)),
+        "bn_bwd_coef");
+  return {coef, dw, db};
+}
+
+bool bn3_conv3_bwd_supported(int64_t c, int64_t c4) { return madnn_bn3_conv3_bwd_supported(c, c4) != 0; }
+
+// K9F: backward of relu(bn3(conv3(a2)) + idt) behind bn3's reduction (coef from bn_bwd_coef), a2 = relu(bn2(y2)):
+// -> (da2, bn2's backward partial sums [rows, 2, C], dW3 [4C, C] fp32 or bf16)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn3_conv3_bwd(const at::Tensor& dout, const at::Tensor& y3,
+                                                             const at::Tensor& mask, const at::Tensor& coef,
+                                                             const at::Tensor& w3, const at::Tensor& a2,
+                                                             const at::Tensor& y2, const at::Tensor& scale2,
+                                                             const at::Tensor& shift2, bool dw_bf16) {
+  const int64_t c4 = y3.size(1), c = a2.size(1);
+  const int64_t M = conv_rows(y3, c4, "y3");
+  TORCH_CHECK(madnn_bn3_conv3_bwd_supported(c, c4), "bn3_conv3_bwd: unsupported channels ", c, " -> ", c4);
+  TORCH_CHECK(M > 0, "bn3_conv3_bwd: empty input");
+  TORCH_CHECK(conv_rows(dout, c4, "dout") == M && dout.dim() == y3.dim(), "bn3_conv3_bwd: dout layout");
+  TORCH_CHECK(conv_rows(a2, c, "a2") == M && a2.dim() == y3.dim(), "bn3_conv3_bwd: a2 layout");
+  TORCH_CHECK(conv_rows(y2, c, "y2") == M && y2.dim() == y3.dim(), "bn3_conv3_bwd: y2 layout");
+  conv_check_w(w3, c4, c);
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() == M * c4 / 8,
+              "bn3_conv3_bwd: ReLU bit mask over y3 required");
+  TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * c4,
+              "bn3_conv3_bwd: fp32 [3, 4C] coefficients");
+  TORCH_CHECK(scale2.numel() == c && shift2.numel() == c && scale2.scalar_type() == at::kFloat &&
+                  shift2.scalar_type() == at::kFloat && scale2.is_contiguous() && shift2.is_contiguous(),
+              "bn3_conv3_bwd: fp32 [C] scale / shift");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(y3.device());
+  auto fo = y3.options().dtype(at::kFloat);
+  const int64_t groups = madnn_bn3_conv3_bwd_groups(M);
+  at::Tensor da2 = conv_out_like(y3, c);
+  at::Tensor part = at::empty({groups, 2, c}, fo);
+  at::Tensor slabs = at::empty({groups, c4, c}, fo);
+  at::Tensor dw = at::empty({c4, c}, y3.options().dtype(dw_bf16 ? at::kBFloat16 : at::kFloat));
+  check(madnn_bn3_conv3_bwd(dout.data_ptr(), y3.data_ptr(), mask.data_ptr<uint8_t>(), coef.data_ptr<float>(),
+                            w3.data_ptr(), a2.data_ptr(), y2.data_ptr(), scale2.data_ptr<float>(),
+                            shift2.data_ptr<float>(), da2.data_ptr(), part.data_ptr<float>(), slabs.data_ptr<float>(),
+                            dw.data_ptr(), dw_bf16 ? 1 : 0, M, c, c4, cur_stream(y3)),
+        "bn3_conv3_bwd");
+  return {da2, part, dw};
 }
 
 // ---- K12 MFMA GEMM (Linear layers) ------------------------------------------------------------
@@ -1493,6 +1564,13 @@ TORCH_LIBRARY(madnn, m) {
       "Tensor partial, bool relu) -> (Tensor, Tensor, Tensor)");
   m.def("conv1x1_wgrad(Tensor dy, Tensor x, bool out_bf16=False) -> Tensor");
   m.def(
+      "bn_bwd_coef(Tensor dy, Tensor x, Tensor mask, Tensor? w, Tensor save_mean, Tensor save_invstd, Tensor scale, "
+      "Tensor shift) -> (Tensor, Tensor, Tensor)");
+  m.def("bn3_conv3_bwd_supported(int c, int c4) -> bool", &bn3_conv3_bwd_supported);
+  m.def(
+      "bn3_conv3_bwd(Tensor dout, Tensor y3, Tensor mask, Tensor coef, Tensor w3, Tensor a2, Tensor y2, Tensor scale2, "
+      "Tensor shift2, bool dw_bf16) -> (Tensor, Tensor, Tensor)");
+  m.def(
       "bn_coef(Tensor x, Tensor? w, Tensor? b, Tensor(a!)? run_mean, Tensor(b!)? run_var, Tensor(c!)? nbt, "
       "float momentum, float eps, Tensor? partial=None) -> Tensor[]");
   m.def("stem_fwd(Tensor x, Tensor wp, bool stats) -> (Tensor, Tensor)");
@@ -1574,6 +1652,8 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("conv1x1_fwd", conv1x1_fwd);
   m.impl("conv1x1_dgrad", conv1x1_dgrad);
   m.impl("conv1x1_wgrad", conv1x1_wgrad);
+  m.impl("bn_bwd_coef", bn_bwd_coef);
+  m.impl("bn3_conv3_bwd", bn3_conv3_bwd);
   m.impl("stem_fwd", stem_fwd);
   m.impl("stem_wgrad", stem_wgrad);
   m.impl("linear_fwd", linear_fwd);

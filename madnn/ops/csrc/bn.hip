@@ -631,10 +631,12 @@ hipError_t madnn_bn_fwd(const void* x, const void* res, void* y, unsigned char* 
   return hipGetLastError();
 }
 
-hipError_t madnn_bn_bwd(const void* dy, const void* x, const unsigned char* mask, int has_res, void* dx, void* dres,
-                        int64_t M, int C, int xdt, int relu, const float* w, const float* save_mean,
-                        const float* save_invstd, const float* scale, const float* shift, float* dw, float* db,
-                        float* coef, float* workspace, hipStream_t stream) {
+// The backward's reduction and finalize without the apply pass: dw / db and the per-channel coefficients
+// coef = ca | cb | cc of dx = ca g + cb x + cc ([3][C]), for a consumer that applies them itself (K9F).
+hipError_t madnn_bn_bwd_coef(const void* dy, const void* x, const unsigned char* mask, int has_res, int64_t M, int C,
+                             int xdt, int relu, const float* w, const float* save_mean, const float* save_invstd,
+                             const float* scale, const float* shift, float* dw, float* db, float* coef,
+                             float* workspace, hipStream_t stream) {
   using namespace madnn;
   if (!madnn_bn_supported(C)) return hipErrorInvalidValue;
   if (M <= 0) return hipSuccess;
@@ -647,12 +649,23 @@ hipError_t madnn_bn_bwd(const void* dy, const void* x, const unsigned char* mask
                        mask, scale, shift, M, C, workspace);
   }));
   MADNN_HIP_CHECK(hipGetLastError());
-  float* ca = coef;
-  float* cb = coef + C;
-  float* cc = coef + 2 * C;
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(32 * kFinSlices), 0, stream, workspace, G, C, 2 * C, C, M, w,
-                     save_mean, save_invstd, dw, db, ca, cb, cc);
-  MADNN_HIP_CHECK(hipGetLastError());
+                     save_mean, save_invstd, dw, db, coef, coef + C, coef + 2 * C);
+  return hipGetLastError();
+}
+
+hipError_t madnn_bn_bwd(const void* dy, const void* x, const unsigned char* mask, int has_res, void* dx, void* dres,
+                        int64_t M, int C, int xdt, int relu, const float* w, const float* save_mean,
+                        const float* save_invstd, const float* scale, const float* shift, float* dw, float* db,
+                        float* coef, float* workspace, hipStream_t stream) {
+  using namespace madnn;
+  if (!madnn_bn_supported(C)) return hipErrorInvalidValue;
+  if (M <= 0) return hipSuccess;
+  MADNN_HIP_CHECK(madnn_bn_bwd_coef(dy, x, mask, has_res, M, C, xdt, relu, w, save_mean, save_invstd, scale, shift, dw,
+                                    db, coef, workspace, stream));
+  const float* ca = coef;
+  const float* cb = coef + C;
+  const float* cc = coef + 2 * C;
   const int64_t total = M * C;
   const int grid = stream_grid(total, 256 * 8, bn_tune().wg_per_cu * kNumCU);
   MADNN_DISPATCH_DT(xdt, XDT, MADNN_BN_VARIANT(relu, has_res, RELU, RES, {

@@ -408,6 +408,275 @@ inline void wgrad_split(int64_t M, int64_t cin, int64_t cout, int& bi, int& bj, 
   splits = (nk + k_chunk - 1) / k_chunk;
 }
 
+// K9F — backward of relu(bn3(conv3(a2)) + idt) behind bn3's reduction, for C = 64 -> 4C = 256 (ResNet
+// layer 1): bn3's apply, conv3's data grad (+ bn2's backward sums, the BNB epilogue) and conv3's weight
+// grad in one kernel, so dy3 = ca g + cb y3 + cc (g = dout under bn3's ReLU bit mask) is formed in
+// registers and never reaches HBM.  Workgroups are persistent over 128-row m tiles.  Per 64-channel co
+// step the bf16-rounded dy3 tile [128 m][64 co] is stored to LDS once and read twice: with row reads as
+// the data grad's B operand (da2[m][ci] += dy3[m][co] W3[co][ci]) and with transpose reads as the weight
+// grad's A operand (dW3[co][ci] += dy3[m][co] a2[m][ci]).  W3 stays in LDS for the whole walk, the
+// 256 x 64 dW3 accumulators in registers (64 per lane); each workgroup stores one fp32 slab and
+// split_reduce_kernel sums the slabs in workgroup order (deterministic).
+// LDS: W3 32 KiB + dy3 2 x 16 KiB + a2 16 KiB = 80 KiB: two workgroups per CU.
+constexpr int kFC = 64, kFC4 = 256, kFBM = 128;
+constexpr int kFW = kFC4 * kFC, kFT = kFBM * 64;  // LDS elements: W3 image, one [128][64] tile
+
+struct FusedArgs {
+  const uint16_t* dout;       // [M][4C]
+  const uint16_t* y3;         // [M][4C] bn3's input
+  const unsigned char* mask;  // bn3's ReLU bit mask over [M][4C], 8 per byte
+  const float* coef;          // bn3's backward coefficients ca | cb | cc, [3][4C]
+  const uint16_t* w3;         // [4C][C]
+  const uint16_t* a2;         // [M][C] relu(bn2(y2))
+  const uint16_t* y2;         // [M][C]
+  const float* sc2;           // bn2's forward scale / shift
+  const float* sh2;
+  uint16_t* da2;              // [M][C]
+  float* partial;             // [grid][2][C] bn2's backward sums
+  float* slabs;               // [grid][4C][C]
+  int64_t M;
+  int m_tiles;
+};
+
+__global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedArgs p) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[kFW + 3 * kFT];
+  uint16_t* const wt = smem;             // [256 co][64 ci], swz<64>
+  uint16_t* const dyt = smem + kFW;      // 2 x [128 m][64 co]
+  uint16_t* const at = dyt + 2 * kFT;    // [128 m][64 ci]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
+  const int G = gridDim.x;
+  // staging and the store epilogue share one thread map: 16-B chunk c8 of the 64-channel rows r8 + 32 i
+  const int c8 = tid & 7, r8 = tid >> 3;
+
+  {
+    Stage<false, kFBM> sw;
+#pragma unroll
+    for (int h = 0; h < kFC4 / kFBM; ++h) {
+      sw.load(p.w3, kFC, h * kFBM, kFC4, 0, kFC, tid);
+      sw.store(wt + h * kFT, tid);
+    }
+  }
+  float ssum[8], ssq[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ssum[e] = ssq[e] = 0.f;
+  f32x16 accw[kFC4 / 64], accd[2];
+#pragma unroll
+  for (int q = 0; q < kFC4 / 64; ++q) accw[q] = zero16();
+  accd[0] = accd[1] = zero16();
+
+  // Register stage of one step.  Addresses are a uniform tile base plus a 32-bit per-thread offset; rows
+  // past M load the last valid row (in bounds) and are zeroed in convert_store, after the affine step: a
+  // zeroed load would still yield cc.  (a2's rows past M then meet zero dy3 rows.)
+  u32x4 sd[4], sy[4], sa[4];
+  unsigned mk[4];
+  // a 32-bit offset the compiler must take as it is: uniform base + this offset is one load, whereas a
+  // 64-bit per-thread address hoisted out of the walk costs two registers for every load of a step
+  auto opaque = [](unsigned v) {
+    asm volatile("" : "+v"(v));
+    return v;
+  };
+  auto row_of = [&](int tile, int i) {  // row r8 + 32 i of the tile, clamped to the rows that exist
+    const int valid = (int)min((int64_t)kFBM, p.M - (int64_t)tile * kFBM);
+    return min(r8 + 32 * i, valid - 1);
+  };
+  auto load_step = [&](int tile, int q) {
+    const int64_t m0 = (int64_t)tile * kFBM;
+    const char* bd = reinterpret_cast<const char*>(p.dout + m0 * kFC4 + q * 64);
+    const char* by = reinterpret_cast<const char*>(p.y3 + m0 * kFC4 + q * 64);
+    const unsigned char* bm = p.mask + m0 * (kFC4 / 8) + q * 8;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned r = (unsigned)row_of(tile, i);
+      const unsigned vo = opaque((r * kFC4 + 8 * c8) * 2u), vm = opaque(r * (kFC4 / 8) + c8);
+      sd[i] = *reinterpret_cast<const u32x4*>(bd + vo);
+      sy[i] = *reinterpret_cast<const u32x4*>(by + vo);
+      mk[i] = (unsigned)(int)reinterpret_cast<const signed char*>(bm)[vm];  // bits 0..7 are used; no zero-extend to wait for
+    }
+  };
+  auto load_a2 = [&](int tile) {
+    const char* ba = reinterpret_cast<const char*>(p.a2 + (int64_t)tile * kFBM * kFC);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      sa[i] = *reinterpret_cast<const u32x4*>(ba + opaque(((unsigned)row_of(tile, i) * kFC + 8 * c8) * 2u));
+  };
+  auto store_a2 = [&]() {
+    // rows 32 apart share the swizzle term: one offset, formed here, plus 4 KiB steps
+    char* a0 = reinterpret_cast<char*>(at) + opaque((unsigned)swz<64>(r8, c8));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(a0 + 4096 * i) = sa[i];
+  };
+  // dy3 of the staged step, rounded to bf16, into an LDS tile.  The coefficient loads (cache hits) are
+  // issued first and fenced, so their latency runs under the wait for the staged data, not after it.
+  auto convert_store = [&](uint16_t* tile_lds, int tile, int q) {
+    const float* cf = p.coef + q * 64 + 8 * c8;
+    f32x4 ca[2], cb[2], cc[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      ca[h] = *reinterpret_cast<const f32x4*>(cf + 4 * h);
+      cb[h] = *reinterpret_cast<const f32x4*>(cf + kFC4 + 4 * h);
+      cc[h] = *reinterpret_cast<const f32x4*>(cf + 2 * kFC4 + 4 * h);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const int valid = (int)min((int64_t)kFBM, p.M - (int64_t)tile * kFBM);
+    unsigned mb[4];  // taken here, so that nothing derived from a mask byte is scheduled (and waited for) earlier
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mb[i] = opaque(mk[i]);
+    u32x4 o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned keep = r8 + 32 * i < valid ? 0xffffffffu : 0u;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float v[2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          const int k = 2 * e + hf;
+          const float d = bf16_to_f32((unsigned short)(hf ? sd[i][e] >> 16 : sd[i][e] & 0xffffu));
+          const float y = bf16_to_f32((unsigned short)(hf ? sy[i][e] >> 16 : sy[i][e] & 0xffffu));
+          const float g = ((mb[i] >> k) & 1u) ? d : 0.f;
+          v[hf] = ca[k >> 2][k & 3] * g + cb[k >> 2][k & 3] * y + cc[k >> 2][k & 3];
+        }
+        o[i][e] = ((unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16)) & keep;
+      }
+    }
+    char* t0 = reinterpret_cast<char*>(tile_lds) + opaque((unsigned)swz<64>(r8, c8));  // as in store_a2
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(t0 + 4096 * i) = o[i];
+  };
+  // da2 tile in LDS: [128 m][64 ci] bf16, 16-B chunks XOR-swizzled per row (gemm_kernel's BI = 64 image)
+  auto out_off = [](int r, int c) { return r * 128 + 16 * (c ^ ((r >> 1) & 7)); };
+
+  int tile = blockIdx.x;  // the launcher keeps grid <= m_tiles
+  load_step(tile, 0);
+  load_a2(tile);
+  convert_store(dyt, tile, 0);
+  store_a2();
+  __syncthreads();
+  int cur = 0;
+  for (;;) {
+    const int ntile = tile + G;
+    const bool more = ntile < p.m_tiles;
+#pragma unroll
+    for (int q = 0; q < kFC4 / 64; ++q) {
+      const bool last = q == kFC4 / 64 - 1;
+      const int nq = last ? 0 : q + 1;
+      const int nt = last ? ntile : tile;
+      const bool go = !last || more;
+      if (go) {  // the next step's global loads are in flight during this step's MFMAs
+        load_step(nt, nq);
+        if (last) load_a2(nt);
+      }
+      uint16_t* buf = dyt + cur * kFT;
+      // data grad: i = ci (W3, column memory), j = m (dy3, row memory); wave w owns m rows 32 w .. +31
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const bf16x8 bv = lds_row(buf, wave * 32 + l32, 2 * s + hh);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) accd[a] = mfma(lds_col<64>(wt, q * 64 + 16 * s, a * 32, lane), bv, accd[a]);
+        // scheduling fences: at most two k steps of operand fragments live (the kernel sits at the 256-VGPR budget)
+        if (s & 1) __builtin_amdgcn_sched_barrier(0);
+      }
+      // weight grad: i = co (dy3, column memory), j = ci (a2, column memory), m the reduction;
+      // wave w owns co block w >> 1 of this step and ci block w & 1
+#pragma unroll
+      for (int s = 0; s < kFBM / 16; ++s) {
+        accw[q] = mfma(lds_col<64>(buf, 16 * s, (wave >> 1) * 32, lane), lds_col<64>(at, 16 * s, (wave & 1) * 32, lane),
+                       accw[q]);
+        if (s & 1) __builtin_amdgcn_sched_barrier(0);
+      }
+      if (go) convert_store(dyt + (cur ^ 1) * kFT, nt, nq);  // the other buffer was last read before the previous barrier
+      if (last) {
+        __syncthreads();  // every wave is done reading buf and the a2 tile
+        if (more) store_a2();
+        char* ot = reinterpret_cast<char*>(buf);
+        const int jr = (int)opaque((unsigned)(wave * 32 + l32));  // the 8 swizzled offsets are formed here, not held
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int ic = a * 32 + 8 * g + 4 * hh;  // first of the lane's 4 consecutive ci
+            const unsigned lo = (unsigned)f32_to_bf16(accd[a][4 * g]) | ((unsigned)f32_to_bf16(accd[a][4 * g + 1]) << 16);
+            const unsigned hi =
+                (unsigned)f32_to_bf16(accd[a][4 * g + 2]) | ((unsigned)f32_to_bf16(accd[a][4 * g + 3]) << 16);
+            *reinterpret_cast<u32x2*>(ot + out_off(jr, ic >> 3) + 8 * ((ic >> 2) & 1)) = u32x2{lo, hi};
+          }
+        accd[0] = accd[1] = zero16();
+        __syncthreads();
+        // full-row 16-B stores of da2, and bn2's backward sums over what is stored (BNB); bn2's scale and
+        // shift are reloaded per tile (cache hits) instead of held in 16 registers across the walk
+        float bs[8], bh[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          bs[e] = p.sc2[8 * c8 + e];
+          bh[e] = p.sh2[8 * c8 + e];
+        }
+        const int64_t m0 = (int64_t)tile * kFBM;
+        const int valid = (int)min((int64_t)kFBM, p.M - m0);
+        char* bo = reinterpret_cast<char*>(p.da2 + m0 * kFC);
+        const char* by2 = reinterpret_cast<const char*>(p.y2 + m0 * kFC);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int r = r8 + 32 * u;
+          if (r < valid) {
+            const unsigned off = opaque(((unsigned)r * kFC + 8 * c8) * 2u);
+            const u32x4 v = *reinterpret_cast<const u32x4*>(ot + opaque((unsigned)out_off(r8, c8)) + 4096 * u);
+            *reinterpret_cast<u32x4*>(bo + off) = v;
+            const u32x4 yv = *reinterpret_cast<const u32x4*>(by2 + off);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+#pragma unroll
+              for (int hf = 0; hf < 2; ++hf) {
+                const int k = 2 * e + hf;
+                const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
+                const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
+                const float gm = yy * bs[k] + bh[k] > 0.f ? g : 0.f;
+                ssum[k] += gm;
+                ssq[k] += gm * yy;
+              }
+            }
+          }
+        }
+      }
+      if (!go) break;
+      __syncthreads();  // next buffer filled; this one (or the da2 tile in it) fully consumed
+      cur ^= 1;
+    }
+    if (!more) break;
+    tile = ntile;
+  }
+
+  // this workgroup's dW3 slab (the thread indices are formed again, not carried in registers through the walk)
+  const int t2 = (int)opaque(threadIdx.x), w2 = t2 >> 6, col2 = t2 & 31, h2 = (t2 >> 5) & 1;
+  float* slab = p.slabs + (int64_t)blockIdx.x * kFW;
+#pragma unroll
+  for (int q = 0; q < kFC4 / 64; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      slab[(q * 64 + (w2 >> 1) * 32 + acc_row(r, h2)) * kFC + (w2 & 1) * 32 + col2] = accw[q][r];
+  // bn2's partial row: sum the 32 row groups through LDS
+  __syncthreads();
+  float* red = reinterpret_cast<float*>(dyt);  // [32][2][64]
+  const int rg = t2 >> 3, cg = t2 & 7;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    red[(rg * 2) * kFC + 8 * cg + e] = ssum[e];
+    red[(rg * 2 + 1) * kFC + 8 * cg + e] = ssq[e];
+  }
+  __syncthreads();
+  if (t2 < 2 * kFC) {
+    const int which = t2 / kFC, ii = t2 % kFC;
+    float v = 0.f;
+    for (int g = 0; g < 32; ++g) v += red[(g * 2 + which) * kFC + ii];
+    p.partial[((int64_t)blockIdx.x * 2 + which) * kFC + ii] = v;
+  }
+}
+
+inline int fused_groups(int64_t M) {
+  const int64_t tiles = (M + kFBM - 1) / kFBM;
+  const int64_t want = tune().fwd_wg < 1 ? 1 : tune().fwd_wg;
+  return (int)(tiles < want ? tiles : want);
+}
+
 }  // namespace conv
 }  // namespace madnn
 
@@ -555,6 +824,48 @@ hipError_t madnn_conv1x1_wgrad(const void* dy, const void* x, void* dw, int dw_b
     hipLaunchKernelGGL(split_reduce_kernel<true>, grid_r, dim3(256), 0, s, ws, (int)splits, n, dw);
   } else {
     hipLaunchKernelGGL(split_reduce_kernel<false>, grid_r, dim3(256), 0, s, ws, (int)splits, n, dw);
+  }
+  return hipGetLastError();
+}
+
+// K9F (bn3_conv3_bwd_kernel): the shapes it is built for
+int madnn_bn3_conv3_bwd_supported(int64_t c, int64_t c4) { return (c == kFC && c4 == kFC4) ? 1 : 0; }
+
+// workgroups = bn2 partial rows ([rows][2][C]) = dW3 slabs ([rows][4C][C] fp32 of workspace)
+int madnn_bn3_conv3_bwd_groups(int64_t M) { return M > 0 ? fused_groups(M) : 0; }
+
+// coef: bn3's ca | cb | cc ([3][4C], bn_bwd_finalize_kernel); partial / slabs: madnn_bn3_conv3_bwd_groups rows;
+// dw: [4C][C] fp32 or (dw_bf16) bf16, the slabs summed in workgroup order
+hipError_t madnn_bn3_conv3_bwd(const void* dout, const void* y3, const unsigned char* mask, const float* coef,
+                               const void* w3, const void* a2, const void* y2, const float* sc2, const float* sh2,
+                               void* da2, float* partial, float* slabs, void* dw, int dw_bf16, int64_t M, int64_t c,
+                               int64_t c4, hipStream_t s) {
+  if (!madnn_bn3_conv3_bwd_supported(c, c4) || M <= 0) return hipErrorInvalidValue;
+  FusedArgs p{};
+  p.dout = static_cast<const uint16_t*>(dout);
+  p.y3 = static_cast<const uint16_t*>(y3);
+  p.mask = mask;
+  p.coef = coef;
+  p.w3 = static_cast<const uint16_t*>(w3);
+  p.a2 = static_cast<const uint16_t*>(a2);
+  p.y2 = static_cast<const uint16_t*>(y2);
+  p.sc2 = sc2;
+  p.sh2 = sh2;
+  p.da2 = static_cast<uint16_t*>(da2);
+  p.partial = partial;
+  p.slabs = slabs;
+  p.M = M;
+  p.m_tiles = (int)((M + kFBM - 1) / kFBM);
+  const int grid = fused_groups(M);
+  hipLaunchKernelGGL(bn3_conv3_bwd_kernel, dim3(grid), dim3(kThreads), 0, s, p);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int64_t n = kFW;
+  const dim3 grid_r((unsigned)((n / 4 + 255) / 256));
+  if (dw_bf16) {
+    hipLaunchKernelGGL(split_reduce_kernel<true>, grid_r, dim3(256), 0, s, slabs, grid, n, dw);
+  } else {
+    hipLaunchKernelGGL(split_reduce_kernel<false>, grid_r, dim3(256), 0, s, slabs, grid, n, dw);
   }
   return hipGetLastError();
 }
