@@ -1281,19 +1281,6 @@ def hidden_supported(h: int) -> bool:
     return h % 8 == 0 and h <= 16384
 
 
-__all__ = [
-    "bucket_pack", "bucket_unpack", "flat_scale_cast", "sgd_step", "adam_step", "grad_norm", "layer_norm",
-    "rms_norm", "batch_norm_act", "bn_supported", "cross_entropy", "attention", "attention_qkvpacked", "attention_supported",
-    "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
-    "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
-    "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",
-    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "conv1x1_supported", "stem_conv", "stem_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
-]
-
-if os.environ.get("MADNN_EAGER_LOAD", "0") == "1":
-    load_kernels()
-
-
 # --------------------------------------------------------------------------- K11
 FUSED_LINEAR = os.environ.get("MADNN_FUSED_LINEAR", "1") != "0"  # models.common.linear routing (A/B switch)
 
@@ -1357,11 +1344,13 @@ def grad_sink(weight: torch.Tensor) -> Optional[torch.Tensor]:
     return space.grad_slot(weight)
 
 
-WGRAD = os.environ.get("MADNN_WGRAD", "auto")  # weight-gradient GEMM: auto (timed per shape) | lt | k12
-_WGRAD_CHOICE: dict = {}
-_GELU_FWD_CHOICE: dict = {}
-_DGELU_CHOICE: dict = {}
-_DGRAD_CHOICE: dict = {}
+# weight-gradient GEMM: auto (timed per shape) | lt | k12 | k12w | k12wh
+WGRAD = os.environ.get("MADNN_WGRAD", "auto")
+
+# The per-shape tuner's tables, table name -> {key tuple: implementation name}, in the shipped
+# file's order; the old per-table names stay as aliases of the same dicts.
+_CHOICES: dict = {"wgrad": {}, "gelu_fwd": {}, "dgelu": {}, "dgrad": {}}
+_WGRAD_CHOICE, _GELU_FWD_CHOICE, _DGELU_CHOICE, _DGRAD_CHOICE = _CHOICES.values()
 _TUNE = {"timed": 0, "table": None}   # run-time timings taken; the shipped table that was loaded
 _TUNE_MS: dict = {}   # (table, key) -> {implementation: ms for 3 calls} of every run-time timing (the A/B record)
 
@@ -1388,8 +1377,7 @@ def load_tuning_table(path: Optional[str] = None) -> int:
     except (OSError, ValueError):
         return 0
     n = 0
-    for name, dst in (("wgrad", _WGRAD_CHOICE), ("gelu_fwd", _GELU_FWD_CHOICE), ("dgelu", _DGELU_CHOICE),
-                      ("dgrad", _DGRAD_CHOICE)):
+    for name, dst in _CHOICES.items():
         for k, v in data.get(name, {}).items():
             dst.setdefault(ast.literal_eval(k), v)
             n += 1
@@ -1401,10 +1389,9 @@ def export_choices(path: str) -> None:
     """Write every per-shape choice this process holds (shipped + timed) in the table format."""
     import json
 
-    data = {"arch": "gfx950", "wgrad": {repr(k): v for k, v in sorted(_WGRAD_CHOICE.items(), key=repr)},
-            "gelu_fwd": {repr(k): v for k, v in sorted(_GELU_FWD_CHOICE.items(), key=repr)},
-            "dgelu": {repr(k): v for k, v in sorted(_DGELU_CHOICE.items(), key=repr)},
-            "dgrad": {repr(k): v for k, v in sorted(_DGRAD_CHOICE.items(), key=repr)}}
+    data = {"arch": "gfx950"}
+    for name, table in _CHOICES.items():
+        data[name] = {repr(k): v for k, v in sorted(table.items(), key=repr)}
     with open(path, "w") as f:
         json.dump(data, f, indent=1)
         f.write("\n")
@@ -1417,12 +1404,10 @@ def sync_choices(group=None, src: int = 0) -> None:
 
     if not dist.is_initialized() or dist.get_world_size(group) <= 1:
         return
-    obj = [(dict(_WGRAD_CHOICE), dict(_GELU_FWD_CHOICE), dict(_DGELU_CHOICE), dict(_DGRAD_CHOICE))]
+    obj = [_CHOICES]
     dist.broadcast_object_list(obj, src=src, group=group)
-    _WGRAD_CHOICE.update(obj[0][0])
-    _GELU_FWD_CHOICE.update(obj[0][1])
-    _DGELU_CHOICE.update(obj[0][2])
-    _DGRAD_CHOICE.update(obj[0][3])
+    for name, table in obj[0].items():
+        _CHOICES[name].update(table)
 
 
 def tuning_timings() -> int:
@@ -1432,12 +1417,8 @@ def tuning_timings() -> int:
 
 def tuning_measurements() -> list:
     """Every per-shape timing this process ran: [{"table", "key", "ms": {impl: ms}, "chosen"}]."""
-    out = []
-    for (tab, key), ms in _TUNE_MS.items():
-        chosen = {"wgrad": _WGRAD_CHOICE, "gelu_fwd": _GELU_FWD_CHOICE, "dgelu": _DGELU_CHOICE,
-                  "dgrad": _DGRAD_CHOICE}[tab].get(key)
-        out.append({"table": tab, "key": repr(key), "ms": {k: round(v, 4) for k, v in ms.items()}, "chosen": chosen})
-    return out
+    return [{"table": tab, "key": repr(key), "ms": {k: round(v, 4) for k, v in ms.items()},
+             "chosen": _CHOICES[tab].get(key)} for (tab, key), ms in _TUNE_MS.items()]
 
 
 def _wgrad_k12_ok(g2, x2, out) -> bool:
@@ -1455,6 +1436,23 @@ def _time_wgrad(fn, iters: int = 3) -> float:
     e.record()
     e.synchronize()
     return s.elapsed_time(e)
+
+
+def _timed_choice(table_name: str, key, cands: dict, default: str) -> str:
+    """The name of the implementation in ``cands`` (name -> callable) to run for ``key``: the one
+    table ``table_name`` holds (the shipped table, :func:`load_tuning_table`, or an earlier timing)
+    when it is among ``cands``; else every candidate is timed once (:func:`_time_wgrad`) and the
+    fastest is stored.  Under graph capture nothing is timed or stored: ``default``."""
+    table = _CHOICES[table_name]
+    choice = table.get(key)
+    if choice in cands:
+        return choice
+    if torch.cuda.is_current_stream_capturing():
+        return default
+    _TUNE["timed"] += 1
+    times = _TUNE_MS[(table_name, key)] = {k: _time_wgrad(f) for k, f in cands.items()}
+    choice = table[key] = min(times, key=times.get)
+    return choice
 
 
 def wgrad_into(g2: torch.Tensor, x2: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -1493,22 +1491,9 @@ def tuned_wgrad(key, lib, k12, k9=None, k12w=None, k12wh=None):
         return k12w()
     if WGRAD == "k12wh" and k12wh is not None:
         return k12wh()
-    cands = {"lib": lib, "k12": k12}
-    if k12w is not None:
-        cands["k12w"] = k12w
-    if k12wh is not None:
-        cands["k12wh"] = k12wh
-    if k9 is not None:
-        cands["k9"] = k9
-    choice = _WGRAD_CHOICE.get(key)
-    if choice not in cands:
-        if torch.cuda.is_current_stream_capturing():
-            return lib()
-        _TUNE["timed"] += 1
-        times = {k: _time_wgrad(f) for k, f in cands.items()}
-        _TUNE_MS[("wgrad", key)] = times
-        choice = _WGRAD_CHOICE[key] = min(times, key=times.get)
-    return cands[choice]()
+    cands = {"lib": lib, "k12": k12, "k12w": k12w, "k12wh": k12wh, "k9": k9}
+    cands = {k: f for k, f in cands.items() if f is not None}
+    return cands[_timed_choice("wgrad", key, cands, "lib")]()
 
 
 def _k9_wgrad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -1565,7 +1550,22 @@ def _lt_linear(x2, weight, bias, residual, gelu):
         return None
 
 
-GELU_FWD = os.environ.get("MADNN_GELU_FWD", "auto")  # GELU Linear forward: auto (timed per shape) | lt | k12
+def _lt_epilogue(x, weight, bias, residual, gelu):
+    """``act(x W^T + b) (+ residual)`` as one hipBLASLt call (:func:`_lt_linear`) on contiguous rows:
+    ``(y, pre)`` in the output's shape (``pre`` only with ``gelu``), or None when that epilogue kind
+    is off or refused (:func:`_lt_ok`)."""
+    if not _lt_ok(x, weight, gelu, residual is not None):
+        return None
+    r2 = residual.reshape(-1, weight.shape[0]).contiguous() if residual is not None else None
+    out = _lt_linear(x.reshape(-1, x.shape[-1]).contiguous(), weight, bias if bias is None else bias.contiguous(),
+                     r2, gelu)
+    if out is None:
+        return None
+    y = out[0].view(*x.shape[:-1], weight.shape[0])
+    return y, (out[1].view_as(y) if gelu else None)
+
+
+GELU_FWD =os.environ.get("MADNN_GELU_FWD", "auto")  # GELU Linear forward: auto (timed per shape) | lt | k12
 
 
 def _k12_fwd_ok(x2: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> bool:
@@ -1584,22 +1584,6 @@ def _k12p_ok(rows: torch.Tensor, weight: torch.Tensor, out_features: int, tokens
     return (_is_dev(rows) and rows.dtype == weight.dtype == torch.bfloat16 and rows.is_contiguous()
             and weight.is_contiguous() and rows.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
             and load_kernels() and bool(torch.ops.madnn.gemmp_supported(out_features, tokens, red, has_bias)))
-
-
-def _timed_choice(table: dict, key, cands: dict, default: str) -> str:
-    """The implementation in ``cands`` that was faster for ``key`` (shipped table, else timed
-    once on first use outside graph capture, like :func:`tuned_wgrad`)."""
-    choice = table.get(key)
-    if choice in cands:
-        return choice
-    if torch.cuda.is_current_stream_capturing():
-        return default
-    _TUNE["timed"] += 1
-    times = {k: _time_wgrad(f) for k, f in cands.items()}
-    name = {id(_GELU_FWD_CHOICE): "gelu_fwd", id(_DGELU_CHOICE): "dgelu", id(_DGRAD_CHOICE): "dgrad"}[id(table)]
-    _TUNE_MS[(name, key)] = times
-    choice = table[key] = min(times, key=times.get)
-    return choice
 
 
 def _gelu_linear_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], kind: int = 1):
@@ -1632,18 +1616,17 @@ def _gelu_linear_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
 
     ok12 = _k12_fwd_ok(x2, weight, bias)
     okp = ok12 and _k12p_ok(x2, weight, weight.shape[0], x2.shape[0], x2.shape[1], bias is not None)
-    choice = GELU_FWD
-    if choice == "k12p" and not okp or choice == "k12" and not ok12:
+    impls = {"lt": lt, "k12": k12, "k12p": k12p}
+    key = (tuple(x2.shape), tuple(weight.shape), bias is not None) + tag
+    if GELU_FWD in impls:   # a pin; on a shape that kernel refuses: lt
+        choice = GELU_FWD if {"lt": True, "k12": ok12, "k12p": okp}[GELU_FWD] else "lt"
+    elif okp:
+        choice = _timed_choice("gelu_fwd", ("p",) + key, {"lt": lt, "k12p": k12p}, "lt")
+    elif ok12:
+        choice = _timed_choice("gelu_fwd", key, {"lt": lt, "k12": k12}, "lt")
+    else:
         choice = "lt"
-    if choice not in ("lt", "k12", "k12p"):
-        choice = "lt"
-        if okp:
-            key = ("p", tuple(x2.shape), tuple(weight.shape), bias is not None) + tag
-            choice = _timed_choice(_GELU_FWD_CHOICE, key, {"lt": lt, "k12p": k12p}, "lt")
-        elif ok12:
-            key = (tuple(x2.shape), tuple(weight.shape), bias is not None) + tag
-            choice = _timed_choice(_GELU_FWD_CHOICE, key, {"lt": lt, "k12": k12}, "lt")
-    y, pre = {"lt": lt, "k12": k12, "k12p": k12p}[choice]()
+    y, pre = impls[choice]()
     return y.view(out_shape), pre.view(out_shape)
 
 
@@ -1672,15 +1655,13 @@ def dgrad_dgelu(g2: torch.Tensor, w2: torch.Tensor, pre2: torch.Tensor, bias_dty
     ok = (bias_dtype in (torch.float32, torch.bfloat16) and _is_dev(pre2) and pre2.dtype == g2.dtype
           and pre2.is_contiguous() and pre2.data_ptr() % 16 == 0
           and _k12p_ok(g2, w2, w2.shape[1], g2.shape[0], g2.shape[1], False))
-    choice = DGELU if DGELU in ("lt", "k12p") else "auto"
-    if choice == "k12p" and not ok:
-        choice = "lt"
-    if choice == "auto":
-        choice = "lt"
-        if ok:
-            key = (tuple(g2.shape), tuple(w2.shape), str(bias_dtype)) + (() if kind == 1 else ("erf",))
-            choice = _timed_choice(_DGELU_CHOICE, key, {"lt": lt, "k12p": k12p}, "lt")
-    return lt() if choice == "lt" else k12p()
+    if DGELU == "lt" or not ok:   # a k12p pin on a shape K12P refuses: lt
+        return lt()
+    if DGELU == "k12p":
+        return k12p()
+    key = (tuple(g2.shape), tuple(w2.shape), str(bias_dtype)) + (() if kind == 1 else ("erf",))
+    cands = {"lt": lt, "k12p": k12p}
+    return cands[_timed_choice("dgelu", key, cands, "lt")]()
 
 
 DGRAD = os.environ.get("MADNN_DGRAD", "auto")  # plain Linear data gradient: auto | lt | ltk | k12p
@@ -1718,7 +1699,27 @@ def dgrad(g2: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     if DGRAD in cands:
         return cands[DGRAD]()
     key = (tuple(g2.shape), tuple(weight.shape))
-    return cands[_timed_choice(_DGRAD_CHOICE, key, cands, "lt")]()
+    return cands[_timed_choice("dgrad", key, cands, "lt")]()
+
+
+def _out_bias_grad(g: torch.Tensor, bias_dtype: torch.dtype) -> torch.Tensor:
+    """The bias gradient of the Linear whose output gradient is ``g``: the column sums its consumer's
+    backward attached to ``g`` (_NormFn, _AttnPackedFn; a reshaped view keeps them on its base), else
+    one K11 pass."""
+    cs = _attached(g, "_madnn_colsum")
+    if cs is not None and cs.numel() == g.shape[-1]:
+        return cs.to(bias_dtype)
+    return bias_grad(g, None, bias_dtype)[0]
+
+
+def _weight_grad(g2: torch.Tensor, x2: torch.Tensor, param: torch.Tensor) -> torch.Tensor:
+    """A Linear's weight gradient, written into the reducer's bucket slot when it has one."""
+    sink = grad_sink(param)
+    if sink is not None and sink.dtype == g2.dtype == x2.dtype and sink.is_contiguous():
+        return wgrad_into(g2, x2, sink)
+    if param.dtype == g2.dtype == x2.dtype and _is_dev(g2):
+        return wgrad_into(g2, x2, torch.empty(param.shape, dtype=param.dtype, device=param.device))
+    return (g2.t() @ x2).to(param.dtype)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -1728,7 +1729,8 @@ class _LinearFn(torch.autograd.Function):
     pre-activation as its AUX output for the backward) and adds the residual stream -- no
     standalone elementwise passes.  Backward: the bias gradient (and the GELU backward) come from
     one K11 pass, the data-gradient GEMM stays on hipBLASLt, and the weight-gradient GEMM
-    (:func:`wgrad_into`: hipBLASLt or K12 split-K, whichever is faster for the shape) writes straight
+    (:func:`wgrad_into`: hipBLASLt or K12 / K12W / K12W16 split-K, whichever is faster for the shape;
+    ``MADNN_WGRAD`` = auto | lt | k12 | k12w | k12wh) writes straight
     into the reducer's bucket when the weight has a :func:`grad_sink`; the residual's gradient is
     the output gradient itself (no copy)."""
 
@@ -1738,66 +1740,33 @@ class _LinearFn(torch.autograd.Function):
         ctx.bias_dtype = bias.dtype if bias is not None else None
         ctx.param = weight  # the Parameter itself (for its grad sink); not modified before backward
         ctx.has_res = residual is not None
-        out = None
-        if (gelu or residual is not None) and _lt_ok(x, weight, gelu, residual is not None):
-            x2 = x.reshape(-1, x.shape[-1])
-            if not x2.is_contiguous():
-                x2 = x2.contiguous()
-            r2 = residual.reshape(-1, weight.shape[0]).contiguous() if residual is not None else None
-            out = _lt_linear(x2, weight, bias if bias is None or bias.is_contiguous() else bias.contiguous(), r2, gelu)
-        if out is not None:
-            y, pre = out
-            y = y.view(*x.shape[:-1], weight.shape[0])
-            if gelu:
-                ctx.save_for_backward(x, weight, pre.view_as(y))
-            else:
-                ctx.save_for_backward(x, weight)
-            return y
-        if gelu:
-            y, pre = _gelu_linear_fwd(x, weight, bias)
-            ctx.save_for_backward(x, weight, pre)
-            return y + residual if residual is not None else y
-        pre = F.linear(x, weight, bias)
-        if gelu:
-            ctx.save_for_backward(x, weight, pre)
-            y = gelu_tanh(pre)
-        else:
-            ctx.save_for_backward(x, weight)
-            y = pre
-        return y + residual if residual is not None else y
+        # a plain Linear (no GELU, no residual) stays on F.linear
+        out = _lt_epilogue(x, weight, bias, residual, gelu) if gelu or residual is not None else None
+        if out is None:
+            out = _gelu_linear_fwd(x, weight, bias) if gelu else (F.linear(x, weight, bias), None)
+            if residual is not None:
+                out = out[0] + residual, out[1]
+        y, pre = out
+        ctx.save_for_backward(*((x, weight, pre) if gelu else (x, weight)))
+        return y
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.gelu:
-            x, weight, pre = ctx.saved_tensors
-        else:
-            (x, weight), pre = ctx.saved_tensors, None
+        x, weight, *pre = ctx.saved_tensors
         db = None
         g_out = g   # the residual's gradient: the upstream gradient itself, not the GELU-scaled one
         if ctx.gelu:
-            db, g = bias_grad(g, pre, ctx.bias_dtype or g.dtype)
+            db, g = bias_grad(g, pre[0], ctx.bias_dtype or g.dtype)
             if ctx.bias_dtype is None:
                 db = None
         elif ctx.bias_dtype is not None and ctx.needs_input_grad[2]:
-            # from the consumer's backward (_NormFn, _AttnPackedFn); a reshaped view keeps it on its base
-            cs = _attached(g, "_madnn_colsum")
-            if cs is not None and cs.numel() == g.shape[-1]:
-                db = cs.to(ctx.bias_dtype)
-            else:
-                db, _ = bias_grad(g, None, ctx.bias_dtype)
+            db = _out_bias_grad(g, ctx.bias_dtype)
         g2 = g.reshape(-1, g.shape[-1])
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = dgrad(g2, weight).view(*x.shape[:-1], weight.shape[1])
         if ctx.needs_input_grad[1]:
-            x2 = x.reshape(-1, x.shape[-1])
-            sink = grad_sink(ctx.param)
-            if sink is not None and sink.dtype == g2.dtype == x2.dtype and sink.is_contiguous():
-                dw = wgrad_into(g2, x2, sink)
-            elif weight.dtype == g2.dtype == x2.dtype and _is_dev(g2):
-                dw = wgrad_into(g2, x2, torch.empty(weight.shape, dtype=weight.dtype, device=weight.device))
-            else:
-                dw = (g2.t() @ x2).to(weight.dtype)
+            dw = _weight_grad(g2, x.reshape(-1, x.shape[-1]), ctx.param)
         ctx.param = None
         return dx, dw, db, None, (g_out if ctx.has_res else None)
 
@@ -1805,14 +1774,9 @@ class _LinearFn(torch.autograd.Function):
 def _linear_residual_fwd(a: torch.Tensor, weight, bias, residual):
     """``a W^T + b (+ residual)``: one hipBLASLt call with the bias / residual epilogue when it
     takes it, else ``F.linear`` + add."""
-    if _lt_ok(a, weight, False, residual is not None):
-        a2 = a.reshape(-1, a.shape[-1])
-        if not a2.is_contiguous():
-            a2 = a2.contiguous()
-        r2 = residual.reshape(-1, weight.shape[0]).contiguous() if residual is not None else None
-        out = _lt_linear(a2, weight, bias if bias is None or bias.is_contiguous() else bias.contiguous(), r2, False)
-        if out is not None:
-            return out[0].view(*a.shape[:-1], weight.shape[0])
+    out = _lt_epilogue(a, weight, bias, residual, False)   # a bias-only Linear too, unlike _LinearFn
+    if out is not None:
+        return out[0]
     # an fp32 bias (kept in fp32 by the data-parallel space) joins a bf16 GEMM in the GEMM's dtype
     y = F.linear(a, weight, bias if bias is None or bias.dtype == a.dtype else bias.to(a.dtype))
     return y + residual if residual is not None else y
@@ -1853,11 +1817,7 @@ class _LinearTeeFn(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         db = None
         if ctx.bias_dtype is not None and ctx.needs_input_grad[2]:
-            cs = _attached(g, "_madnn_colsum")  # the attention backward's dQKV column sums
-            if cs is not None and cs.numel() == g.shape[-1]:
-                db = cs.to(ctx.bias_dtype)
-            else:
-                db, _ = bias_grad(g, None, ctx.bias_dtype)
+            db = _out_bias_grad(g, ctx.bias_dtype)  # the attention backward's dQKV column sums
         g2 = g.reshape(-1, g.shape[-1])
         dx = dw = None
         if ctx.needs_input_grad[0]:
@@ -1878,16 +1838,6 @@ def linear_tee(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     if not torch.is_grad_enabled() or not _is_dev(x) or weight.shape[0] % 8:
         return F.linear(x, weight, bias if bias is None or bias.dtype == x.dtype else bias.to(x.dtype)), x
     return _LinearTeeFn.apply(x, weight, bias)
-
-
-def _weight_grad(g2: torch.Tensor, x2: torch.Tensor, param: torch.Tensor) -> torch.Tensor:
-    """A Linear's weight gradient, written into the reducer's bucket slot when it has one."""
-    sink = grad_sink(param)
-    if sink is not None and sink.dtype == g2.dtype == x2.dtype and sink.is_contiguous():
-        return wgrad_into(g2, x2, sink)
-    if param.dtype == g2.dtype == x2.dtype and _is_dev(g2):
-        return wgrad_into(g2, x2, torch.empty(param.shape, dtype=param.dtype, device=param.device))
-    return (g2.t() @ x2).to(param.dtype)
 
 
 class _GeluMLPFn(torch.autograd.Function):
@@ -1925,13 +1875,7 @@ class _GeluMLPFn(torch.autograd.Function):
         p1, p2 = ctx.params
         ctx.params = None
         need = ctx.needs_input_grad
-        db2 = None
-        if ctx.b2_dtype is not None and need[4]:
-            cs = _attached(g, "_madnn_colsum")
-            if cs is not None and cs.numel() == g.shape[-1]:
-                db2 = cs.to(ctx.b2_dtype)
-            else:
-                db2, _ = bias_grad(g, None, ctx.b2_dtype)
+        db2 = _out_bias_grad(g, ctx.b2_dtype) if ctx.b2_dtype is not None and need[4] else None
         g2 = g.reshape(-1, g.shape[-1])
         if not g2.is_contiguous():
             g2 = g2.contiguous()
@@ -1975,18 +1919,28 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     if residual is not None and residual.shape[:-1] != x.shape[:-1]:
         raise ValueError("linear: residual must have the output's shape")
     if not torch.is_grad_enabled() or (not force_fn and (not _is_dev(x) or weight.shape[0] % 8)):
-        if not torch.is_grad_enabled() and _is_dev(x) and (gelu or residual is not None) \
-                and _lt_ok(x, weight, gelu, residual is not None) \
-                and weight.shape[0] % 8 == 0:
-            x2 = x.reshape(-1, x.shape[-1]).contiguous()
-            r2 = residual.reshape(-1, weight.shape[0]).contiguous() if residual is not None else None
-            out = _lt_linear(x2, weight, bias, r2, gelu)
+        if not torch.is_grad_enabled() and _is_dev(x) and (gelu or residual is not None) and weight.shape[0] % 8 == 0:
+            out = _lt_epilogue(x, weight, bias, residual, gelu)
             if out is not None:
-                return out[0].view(*x.shape[:-1], weight.shape[0])
+                return out[0]
         y = F.linear(x, weight, bias)
         y = F.gelu(y, approximate="tanh") if gelu else y
         return y + residual if residual is not None else y
     return _LinearFn.apply(x, weight, bias, gelu, residual)
 
+
+__all__ = [
+    "bucket_pack", "bucket_unpack", "flat_scale_cast", "sgd_step", "adam_step", "grad_norm", "layer_norm",
+    "rms_norm", "batch_norm_act", "bn_supported", "cross_entropy", "attention", "attention_qkvpacked", "attention_supported",
+    "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
+    "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
+    "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",
+    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "conv1x1_supported", "stem_conv", "stem_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
+    "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
+    "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
+]
+
+if os.environ.get("MADNN_EAGER_LOAD", "0") == "1":
+    load_kernels()
 
 load_tuning_table()

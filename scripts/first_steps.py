@@ -94,8 +94,7 @@ def main():
                     "timing_s": round(timings["s"] - s0, 3)})
         print(json.dumps(per[-1]), flush=True)
     rec = {"model": args.model, "batch": args.batch, "steps": per,
-           "wgrad_choices": {str(k): v for k, v in ops._WGRAD_CHOICE.items()},
-           "gelu_fwd_choices": {str(k): v for k, v in ops._GELU_FWD_CHOICE.items()},
+           **{f"{name}_choices": {str(k): v for k, v in table.items()} for name, table in ops._CHOICES.items()},
            "miopen_cache_bytes_before": cache0, "miopen_cache_bytes_after": _dir_bytes(cache),
            "miopen_cache_dir": str(cache)}
     print(json.dumps(rec), flush=True)

@@ -60,8 +60,7 @@ def main():
     madnn.init()
     if args.keep_table:
         ops.load_kernels()
-        tables = {"wgrad": ops._WGRAD_CHOICE, "gelu_fwd": ops._GELU_FWD_CHOICE, "dgelu": ops._DGELU_CHOICE,
-                  "dgrad": ops._DGRAD_CHOICE}
+        tables = ops._CHOICES
         for item in [v for v in args.retime.split(",") if v]:
             tab, kind = item.split(":")
             for k in [k for k in tables[tab] if k and (kind == "*" or k[0] == kind)]:
@@ -141,8 +140,7 @@ def main():
     (out / "record.json").write_text(json.dumps(rec, indent=1) + "\n")
     # the per-shape A/B behind every choice (ms for 3 calls of each implementation)
     (out / "measurements.json").write_text(json.dumps(ops.tuning_measurements(), indent=1) + "\n")
-    print(json.dumps({"choices": len(ops._WGRAD_CHOICE) + len(ops._GELU_FWD_CHOICE) + len(ops._DGELU_CHOICE)
-                      + len(ops._DGRAD_CHOICE),
+    print(json.dumps({"choices": sum(len(t) for t in ops._CHOICES.values()),
                       "miopen_db": sorted(p.name for p in db.iterdir())}), flush=True)
 
 

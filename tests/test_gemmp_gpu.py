@@ -160,6 +160,75 @@ def test_gelu_mlp_node_against_fp32(cuda, impl, approx, monkeypatch):
         assert _rel(a, b) < 2e-2, (name, _rel(a, b))
 
 
+def test_tuner_keys_and_candidates_at_the_smallest_all_candidate_shape(cuda, monkeypatch):
+    """512 tokens, 256 -> 512 -> 256 features: the smallest shape every candidate takes (256-multiples
+    for K12P, a 128-multiple of tokens for K12W16).  With every switch at auto, one MLP node and one
+    plain Linear, forward and backward, add exactly the shipped table's key formats to the tuner's
+    registry, each timed over its full candidate set; the gradients match the fp32 composition."""
+    from madnn import ops
+
+    for name in ("WGRAD", "DGRAD", "DGELU", "GELU_FWD"):
+        monkeypatch.setattr(ops, name, "auto")
+    T, H, I = 512, 256, 512
+    want = {"gelu_fwd": {("p", (T, H), (I, H), True)},
+            "dgelu": {((T, H), (H, I), "torch.float32")},
+            "dgrad": {((T, I), (I, H))},
+            "wgrad": {("linear", T, H, I), ("linear", T, I, H)}}
+    cands = {"gelu_fwd": {"lt", "k12p"}, "dgelu": {"lt", "k12p"}, "wgrad": {"lib", "k12", "k12w", "k12wh"},
+             "dgrad": {"lt", "ltk"} | ({"k12p"} if _ops().gemmp_supported(H, T, I, False) else set())}
+    tables = {"gelu_fwd": ops._GELU_FWD_CHOICE, "dgelu": ops._DGELU_CHOICE, "dgrad": ops._DGRAD_CHOICE,
+              "wgrad": ops._WGRAD_CHOICE}
+
+    def forget():
+        for tab, keys in want.items():
+            for k in keys:
+                tables[tab].pop(k, None)
+                ops._TUNE_MS.pop((tab, k), None)
+
+    forget()   # an earlier test of this process may have met one of the shapes
+    timed0 = ops.tuning_timings()
+    before = {tab: set(t) for tab, t in tables.items()}
+    torch.manual_seed(7)
+    x = torch.randn(T, H, device="cuda").bfloat16().requires_grad_(True)
+    w1 = (torch.randn(I, H, device="cuda") * H ** -0.5).bfloat16().requires_grad_(True)
+    b1 = (torch.randn(I, device="cuda") * 0.1).requires_grad_(True)
+    w2 = (torch.randn(H, I, device="cuda") * I ** -0.5).bfloat16().requires_grad_(True)
+    b2 = (torch.randn(H, device="cuda") * 0.1).requires_grad_(True)
+    # the plain Linear adds its bias in F.linear, which takes it in the activations' dtype only
+    bz = b1.detach().bfloat16().requires_grad_(True)
+    try:
+        y = ops.gelu_mlp(x, w1, b1, w2, b2)
+        gy = torch.randn_like(y)
+        got = torch.autograd.grad(y, (x, w1, b1, w2, b2), gy)
+        z = ops.linear(x, w1, bz)
+        gz = torch.randn_like(z)
+        got_z = torch.autograd.grad(z, (x, w1, bz), gz)
+        for tab, t in tables.items():
+            assert set(t) - before[tab] == want[tab], tab
+        # dw1 of the MLP and dw of the Linear are the same shape: one timing
+        assert ops.tuning_timings() == timed0 + sum(len(keys) for keys in want.values())
+        timed = {(m["table"], m["key"]): m for m in ops.tuning_measurements()}
+        for tab, keys in want.items():
+            for k in keys:
+                m = timed[(tab, repr(k))]
+                assert set(m["ms"]) == cands[tab], (tab, k, m)
+                assert m["chosen"] == tables[tab][k] and m["chosen"] in cands[tab], (tab, k, m)
+    finally:
+        forget()
+        ops._TUNE["timed"] = timed0
+    xs = [t.detach().float().requires_grad_(True) for t in (x, w1, b1, w2, b2)]
+    ref_y = F.linear(F.gelu(F.linear(xs[0], xs[1], xs[2]), approximate="tanh"), xs[3], xs[4])
+    ref = torch.autograd.grad(ref_y, xs, gy.float())
+    assert _rel(y, ref_y) < 1e-2
+    for name, a, b in zip(("dx", "dw1", "db1", "dw2", "db2"), got, ref):
+        assert _rel(a, b) < 2e-2, (name, _rel(a, b))
+    zs = xs[:2] + [bz.detach().float().requires_grad_(True)]
+    ref_z = F.linear(*zs)
+    assert _rel(z, ref_z) < 1e-2
+    for name, a, b in zip(("dx", "dw", "db"), got_z, torch.autograd.grad(ref_z, zs, gz.float())):
+        assert _rel(a, b) < 2e-2, (name, _rel(a, b))
+
+
 @pytest.mark.parametrize("impl", ["k12", "lt"])
 def test_gelu_mlp_erf_on_ragged_rows(cuda, impl, monkeypatch):
     """Rows that are not a multiple of 256 (no K12P): the exact-GELU MLP on K12's one-tile epilogue

@@ -757,6 +757,135 @@ def test_tuning_table_roundtrip(tmp_path):
         ops.load_tuning_table()
 
 
+def test_tuner_contract_through_tuned_wgrad(monkeypatch):
+    """The per-shape tuner as ``tuned_wgrad`` shows it: an unknown key is timed once (every offered
+    candidate, the fastest stored and run, the timing counted and recorded), a stored choice is not
+    timed again, a stored choice that is not offered is timed afresh among the offered ones, and
+    under graph capture the default runs and nothing is recorded."""
+    key, key2 = ("linear", 7, 11, 13), ("linear", 7, 11, 17)   # not in the shipped table
+    assert key not in ops._WGRAD_CHOICE and key2 not in ops._WGRAD_CHOICE
+    monkeypatch.setattr(ops, "WGRAD", "auto")
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    ms = {"lib": 3.0, "k12": 1.0, "k12w": 2.0}
+    monkeypatch.setattr(ops, "_time_wgrad", lambda fn: ms[fn()])
+    fakes = {n: (lambda n=n: n) for n in ("lib", "k12", "k12w")}
+
+    def run(k):
+        return ops.tuned_wgrad(k, fakes["lib"], fakes["k12"], k12w=fakes["k12w"])
+
+    timed0, n_ms0 = ops.tuning_timings(), len(ops.tuning_measurements())
+    try:
+        assert run(key) == "k12" and ops._WGRAD_CHOICE[key] == "k12"
+        assert ops.tuning_timings() == timed0 + 1
+        rec = ops.tuning_measurements()
+        assert len(rec) == n_ms0 + 1
+        assert rec[-1] == {"table": "wgrad", "key": repr(key), "ms": ms, "chosen": "k12"}
+
+        def boom(fn):
+            raise AssertionError("a stored choice was timed again")
+
+        monkeypatch.setattr(ops, "_time_wgrad", boom)
+        assert run(key) == "k12" and ops.tuning_timings() == timed0 + 1
+        # a stored choice whose candidate is not offered: timed afresh among the offered ones
+        ops._WGRAD_CHOICE[key] = "k12wh"
+        monkeypatch.setattr(ops, "_time_wgrad", lambda fn: ms[fn()])
+        assert run(key) == "k12" and ops._WGRAD_CHOICE[key] == "k12"
+        assert ops.tuning_timings() == timed0 + 2 and len(ops.tuning_measurements()) == n_ms0 + 1
+        # under graph capture: the library kernel, nothing timed, nothing stored
+        monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+        monkeypatch.setattr(ops, "_time_wgrad", boom)
+        assert run(key2) == "lib"
+        assert key2 not in ops._WGRAD_CHOICE and ("wgrad", key2) not in ops._TUNE_MS
+        assert ops.tuning_timings() == timed0 + 2
+    finally:
+        for k in (key, key2):
+            ops._WGRAD_CHOICE.pop(k, None)
+            ops._TUNE_MS.pop(("wgrad", k), None)
+        ops._TUNE["timed"] = timed0
+
+
+def test_shipped_tuning_table_exports_byte_identical_and_reloads(tmp_path):
+    """Exporting straight after import reproduces the shipped table byte for byte (table order, key
+    reprs, sorting, indentation), and loading that export into empty tables restores all four."""
+    tables = ("_WGRAD_CHOICE", "_GELU_FWD_CHOICE", "_DGELU_CHOICE", "_DGRAD_CHOICE")
+    p = tmp_path / "t.json"
+    ops.export_choices(str(p))
+    with open(ops.TUNE_TABLE, "rb") as f:
+        assert p.read_bytes() == f.read()
+    saved = {n: dict(getattr(ops, n)) for n in tables}
+    assert all(saved.values())
+    for n in tables:
+        getattr(ops, n).clear()
+    try:
+        assert ops.load_tuning_table(str(p)) == sum(len(v) for v in saved.values())
+        for n in tables:
+            assert getattr(ops, n) == saved[n], n
+    finally:
+        for n in tables:
+            getattr(ops, n).update(saved[n])
+        ops.load_tuning_table()
+
+
+@pytest.mark.parametrize("node", ["linear", "tee", "mlp"])
+def test_attached_column_sum_is_the_output_bias_gradient_of_every_linear_node(node, monkeypatch):
+    """A consumer's backward attaches the column sums of the gradient it returns; each Linear node
+    (_LinearFn, _LinearTeeFn, _GeluMLPFn) takes them as its output-side bias gradient instead of
+    running K11, and falls back to ``bias_grad`` when the attached sum has the wrong length."""
+    n, h = 8, 16
+
+    class Consumer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, y, extra):
+            ctx.extra = extra
+            return y.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            cs = g.reshape(-1, n).sum(0)
+            ops._attach(g, "_madnn_colsum", torch.cat([cs, cs[:ctx.extra]]))
+            return g, None
+
+    plain = []   # bias_grad calls without a GELU input: the output-side bias gradients
+    real = ops.bias_grad
+
+    def spy(dy, pre=None, bias_dtype=None, kind=1):
+        if pre is None:
+            plain.append(tuple(dy.shape))
+        return real(dy, pre, bias_dtype, kind)
+
+    monkeypatch.setattr(ops, "bias_grad", spy)
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(3, 5, n, dtype=torch.float64, generator=g)
+    gy = torch.randn(3, 5, n, dtype=torch.float64, generator=g)
+    w = torch.randn(n, n, dtype=torch.float64, generator=g).requires_grad_(True)
+    b = torch.randn(n, dtype=torch.float64, generator=g).requires_grad_(True)
+    w1 = torch.randn(h, n, dtype=torch.float64, generator=g).requires_grad_(True)
+    b1 = torch.randn(h, dtype=torch.float64, generator=g).requires_grad_(True)
+    w2 = torch.randn(n, h, dtype=torch.float64, generator=g).requires_grad_(True)
+
+    def fused():
+        if node == "linear":
+            return ops.linear(x, w, b, force_fn=True)
+        if node == "tee":
+            return ops._LinearTeeFn.apply(x, w, b)[0]
+        return ops._GeluMLPFn.apply(x, w1, b1, w2, b, None, 1)
+
+    def eager():
+        if node == "mlp":
+            return F.linear(F.gelu(F.linear(x, w1, b1), approximate="tanh"), w2, b)
+        return F.linear(x, w, b)
+
+    want, = torch.autograd.grad(eager(), b, gy)
+    for extra, fallbacks in ((0, 0), (1, 1)):   # the right length; one element too many
+        plain.clear()
+        y = fused()
+        assert type(y.grad_fn).__name__ == {"linear": "_LinearFnBackward", "tee": "_LinearTeeFnBackward",
+                                            "mlp": "_GeluMLPFnBackward"}[node]
+        got, = torch.autograd.grad(Consumer.apply(y, extra), b, gy)
+        torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+        assert len(plain) == fallbacks, (extra, plain)
+
+
 def test_planner_prices_pipelines_with_the_engine_transport():
     """transport_time = the simulated makespan of the engine's own transport: with free transfers
     it is the compute-only schedule (M*chunk / (1 - bubble)); with transfers it grows, and it is
