@@ -12,7 +12,10 @@ forward with the BatchNorm statistics in its epilogue, MFMA weight gradient); th
 NHWC kernel (K7, byte argmax + gather backward); every
 BatchNorm is madnn's fused NHWC kernel (K5) with the following ReLU and, at the
 end of each block, the residual add folded in: ``relu(bn3(conv3(h)) + idt)`` is
-one kernel forward and one backward.  The network runs channels_last (NHWC) in
+one kernel forward and one backward.  In layer 1 (64 -> 256 channels) the backward of that tail is
+K9F: bn3's apply and conv3's data and weight gradients in one kernel, and in the downsample block
+the same kernel once more for the downsample BatchNorm and convolution
+(``ops.bn2_conv3_bn3_add_relu`` / ``ops.bn2_conv3_bn3_add_bn_relu``).  The network runs channels_last (NHWC) in
 bf16 with fp32 BatchNorm parameters — the layout MIOpen's gfx950 implicit-GEMM
 convolutions prefer.
 """
@@ -27,7 +30,8 @@ from torch import nn
 from ..nn.conv import FusedConv2d
 from ..nn.norm import FusedBatchNorm2d as BN
 from ..nn.norm import FusedGlobalAvgPool2d, FusedMaxPool2d
-from ..ops import (batch_norm_add_bn_relu, bn2_conv3_bn3_add_relu, bn2_conv3_bn3_supported, bn_relu_conv1x1,
+from ..ops import (batch_norm_add_bn_relu, bn2_conv3_bn3_add_bn_relu, bn2_conv3_bn3_add_bn_relu_supported,
+                   bn2_conv3_bn3_add_relu, bn2_conv3_bn3_supported, bn_relu_conv1x1,
                    bn_relu_conv1x1_epi_supported, bn_relu_conv3x3, conv1x1_route,
                    bn_relu_conv3x3_supported, bn_relu_maxpool, bn_relu_maxpool_supported)
 
@@ -102,6 +106,17 @@ class Bottleneck(nn.Module):
                 # sub: conv1 hands over the compact x[:, :, ::2, ::2] and the stride-2 downsample
                 # runs as a stride-1 1x1 on it (K9, BN statistics from its epilogue); its compact
                 # input gradient is added into conv1's data grad at the even pixels
+                ds, bn_ds = self.downsample
+                if not sub and self._k9f_dual(y, xf):
+                    # layer 1's downsample block: K9F once per convolution; the downsample convolution is
+                    # issued inside the function, and neither dy3 nor dyd is written in the backward
+                    y, st = self._bn1_conv2(y, st)
+                    if self._k9f_dual(y, xf):
+                        return bn2_conv3_bn3_add_bn_relu(y, self.bn2, self.conv3.weight, self.bn3, xf, ds.weight,
+                                                         bn_ds, stats_in=st)
+                    yd, std = ds(xf, stats=True)
+                    y, st = self._bn2_conv3(y, st)
+                    return batch_norm_add_bn_relu(y, yd, self.bn3, bn_ds, st, std)
                 yd, std = (self.downsample[0].forward_subsampled(xf, stats=True) if sub
                            else self.downsample[0](xf, stats=True))
                 y, st = self._bn1_conv2(y, st)
@@ -139,6 +154,15 @@ class Bottleneck(nn.Module):
             return bn_relu_conv1x1(y, self.bn2, self.conv3.weight, stats_in=st, stats=True)
         out = self.bn2(y, relu=True, stats=st)
         return self.conv3(out, stats=True)
+
+    def _k9f_dual(self, y, xf) -> bool:
+        """K9F on conv3 and on a stride-1 downsample convolution (ops.bn2_conv3_bn3_add_bn_relu), asked with
+        conv1's output (conv2 at stride 1 keeps its shape) and again with conv2's."""
+        ds = self.downsample
+        return (isinstance(y, torch.Tensor) and isinstance(xf, torch.Tensor) and isinstance(self.bn2, BN)
+                and isinstance(self.conv3, FusedConv2d) and self.conv2.stride == (1, 1) and self.conv3._k9(y)
+                and ds[0]._k9(xf) and bn2_conv3_bn3_add_bn_relu_supported(
+                    y, self.bn2, self.conv3.weight, self.bn3, xf, ds[0].weight, ds[1]))
 
     def _dual_bn(self) -> bool:
         ds = self.downsample

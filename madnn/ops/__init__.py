@@ -975,6 +975,84 @@ def bn2_conv3_bn3_add_relu(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, idt: to
     return _BN2Conv3BN3Fn.apply(y2, w3, bn2.weight, bn2.bias, bn3.weight, bn3.bias, idt, bn2, bn3, stats_in)
 
 
+class _BN2Conv3BN3DualFn(torch.autograd.Function):
+    """``relu(bn3(conv3(relu(bn2(y2)))) + bn_ds(conv_ds(xf)))`` in training, the tail of a ResNet
+    downsample bottleneck with a stride-1 downsample (K9F on both convolutions).  Forward: the kernels of
+    :class:`_BNReluConv1x1EpiFn`, :class:`_Conv1x1Fn` and :class:`_BNDualFn`, unchanged.  Backward: the dual
+    reduction + its two finalizes, then the fused kernel once per convolution -- each forms its own
+    ``dy = ca g + cb y + cc`` in registers from ``dout``, the ReLU bit mask and ``y3`` (or ``yd``), so neither
+    ``dy3`` nor ``dyd`` is written -- then bn2's finalize + apply.  ``xf``'s gradient is a plain tensor."""
+
+    @staticmethod
+    def forward(ctx, y2, w3, bn2_w, bn2_b, bn3_w, bn3_b, xf, w_ds, bnd_w, bnd_b, bn2, bn3, bn_ds, stats_in):
+        a2, mean2, invstd2, scale2, shift2, _ = torch.ops.madnn.bn_fwd(
+            y2, None, bn2_w, bn2_b, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked, True,
+            float(bn2.momentum), float(bn2.eps), True, stats_in)
+        y3, part = torch.ops.madnn.conv1x1_fwd(a2, w3, True)
+        yd, part_d = torch.ops.madnn.conv1x1_fwd(xf, w_ds, True)
+        out, mask, mean3, invstd3, _, _, mean_d, invstd_d, _, _ = torch.ops.madnn.bn_fwd_dual(
+            y3, yd, bn3_w, bn3_b, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked, float(bn3.momentum),
+            float(bn3.eps), part, bnd_w, bnd_b, bn_ds.running_mean, bn_ds.running_var, bn_ds.num_batches_tracked,
+            float(bn_ds.momentum), float(bn_ds.eps), part_d)
+        ctx.save_for_backward(y2, a2, w3, y3, xf, w_ds, yd, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3,
+                              invstd3, bnd_w, mean_d, invstd_d)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (y2, a2, w3, y3, xf, w_ds, yd, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3, invstd3, bnd_w,
+         mean_d, invstd_d) = ctx.saved_tensors
+        if dout.dtype != y3.dtype or dout.stride() != y3.stride():
+            dout = torch.empty_like(y3).copy_(dout)
+        coef, dbw3, dbb3, dbwd, dbbd = torch.ops.madnn.bn_bwd_dual_coef(dout, y3, yd, mask, bn3_w, mean3, invstd3,
+                                                                        bnd_w, mean_d, invstd_d)
+        da2, part, dw3 = torch.ops.madnn.bn3_conv3_bwd(dout, y3, mask, coef[:3], w3, a2, y2, scale2, shift2,
+                                                       w3.dtype == torch.bfloat16)
+        dxf, _, dwd = torch.ops.madnn.bn3_conv3_bwd(dout, yd, mask, coef[3:], w_ds, xf, None, None, None,
+                                                    w_ds.dtype == torch.bfloat16)
+        dy2, dbw2, dbb2 = torch.ops.madnn.bn_bwd_ext(da2, y2, bn2_w, mean2, invstd2, scale2, shift2, part, True)
+        need = ctx.needs_input_grad
+        need2, need3, needd = need[2] or need[3], need[4] or need[5], need[8] or need[9]
+        return (dy2, dw3.to(w3.dtype).view(w3.shape), dbw2 if need2 else None, dbb2 if need2 else None,
+                dbw3 if need3 else None, dbb3 if need3 else None, dxf, dwd.to(w_ds.dtype).view(w_ds.shape),
+                dbwd if needd else None, dbbd if needd else None, None, None, None, None)
+
+
+# A/B switch: K9F also on the layer-1 downsample block (both convolutions); honoured while _BN3_CONV3_FUSED is on
+_BN3_CONV3_DUAL = os.environ.get("MADNN_BN3_CONV3_DUAL", "1") != "0"
+
+
+def bn2_conv3_bn3_add_bn_relu_supported(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, xf: torch.Tensor,
+                                        w_ds: torch.Tensor, bn_ds) -> bool:
+    """Inputs :func:`bn2_conv3_bn3_add_bn_relu` runs with the fused backward kernel on both convolutions:
+    the layer-1 downsample bottleneck shape (conv3 and a stride-1 downsample convolution both 64 -> 256
+    channels, ``xf`` of ``y2``'s pixels), all three BatchNorms training with fp32 affine parameters, and both
+    convolutions' forward and data grad on K9.  (That ``w_ds`` belongs to a stride-1 1x1 convolution is the
+    caller's to check.)"""
+    def ok(m):
+        return (m.training and m.track_running_stats and m.affine and m.momentum is not None
+                and m.weight.dtype == torch.float32)
+    if not (_BN3_CONV3_FUSED and _BN3_CONV3_DUAL and isinstance(y2, torch.Tensor) and isinstance(xf, torch.Tensor)):
+        return False
+    c, c4 = y2.size(1), w3.size(0)
+    return (bn_relu_conv1x1_epi_supported(y2, bn2, w3) and native_available()
+            and bool(torch.ops.madnn.bn3_conv3_bwd_supported(c, c4)) and conv1x1_route(c, c4)[:2] == ("k9", "k9")
+            and conv1x1_supported(xf, w_ds) and xf.size(1) == c and w_ds.size(0) == c4
+            and ok(bn2) and ok(bn3) and ok(bn_ds) and bn3.weight.numel() == c4 and bn_ds.weight.numel() == c4
+            and y2.requires_grad and torch.is_grad_enabled()
+            and xf.dtype == y2.dtype and xf.dim() == y2.dim() and xf.size(0) == y2.size(0)
+            and xf.shape[2:] == y2.shape[2:])
+
+
+def bn2_conv3_bn3_add_bn_relu(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, xf: torch.Tensor, w_ds: torch.Tensor,
+                              bn_ds, stats_in: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``relu(bn3(conv1x1(relu(bn2(y2)), w3)) + bn_ds(conv1x1(xf, w_ds)))`` (see :class:`_BN2Conv3BN3DualFn`);
+    the caller checks :func:`bn2_conv3_bn3_add_bn_relu_supported`."""
+    _need_native("bn2_conv3_bn3_add_bn_relu")
+    return _BN2Conv3BN3DualFn.apply(y2, w3, bn2.weight, bn2.bias, bn3.weight, bn3.bias, xf, w_ds, bn_ds.weight,
+                                    bn_ds.bias, bn2, bn3, bn_ds, stats_in)
+
+
 class _BNReluMaxPoolFn(torch.autograd.Function):
     """``max_pool2d(relu(bn(y)), 3, 2, 1)`` in training (ResNet's stem): the BN apply + ReLU run
     inside the pool's window loads; backward gathers the pool gradient per input pixel inside the
@@ -1935,7 +2013,7 @@ __all__ = [
     "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
     "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
     "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",
-    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "conv1x1_supported", "stem_conv", "stem_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
+    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "stem_conv", "stem_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
 ]

@@ -77,6 +77,9 @@ hipError_t madnn_bn_fwd_dual(const void*, const void*, void*, unsigned char*, in
 hipError_t madnn_bn_bwd_dual(const void*, const void*, const void*, const unsigned char*, void*, void*, int64_t, int,
                              const float*, const float*, const float*, const float*, const float*, const float*,
                              float*, float*, float*, float*, float*, float*, hipStream_t);
+hipError_t madnn_bn_bwd_dual_coef(const void*, const void*, const void*, const unsigned char*, int64_t, int,
+                                  const float*, const float*, const float*, const float*, const float*, const float*,
+                                  float*, float*, float*, float*, float*, float*, hipStream_t);
 hipError_t madnn_bn_bwd_coef(const void*, const void*, const unsigned char*, int, int64_t, int, int, int, const float*,
                              const float*, const float*, const float*, const float*, float*, float*, float*, float*,
                              hipStream_t);
@@ -541,6 +544,38 @@ std::vector<at::Tensor> bn_bwd_dual(const at::Tensor& dy, const at::Tensor& x, c
   return out;
 }
 
+// bn_bwd_dual without the apply pass: the same reduction and finalizes
+// -> (coef [6, C] = ca | cb | cc of dx, then of dr; dw, db, dw_r, db_r)
+std::vector<at::Tensor> bn_bwd_dual_coef(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& r,
+                                         const at::Tensor& mask, const c10::optional<at::Tensor>& w,
+                                         const at::Tensor& save_mean, const at::Tensor& save_invstd,
+                                         const c10::optional<at::Tensor>& w_r, const at::Tensor& save_mean_r,
+                                         const at::Tensor& save_invstd_r) {
+  check_dev(x, "x");
+  const int64_t C = x.size(1);
+  const int64_t M = bn_rows(x, C);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "bn_bwd_dual_coef: bf16 only");
+  TORCH_CHECK(r.sizes() == x.sizes() && r.strides() == x.strides() && r.scalar_type() == x.scalar_type(),
+              "bn_bwd_dual_coef: residual layout");
+  TORCH_CHECK(dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type(),
+              "bn_bwd_dual_coef: dy / x of one layout");
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() == x.numel() / 8,
+              "bn_bwd_dual_coef: ReLU bit mask required");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto fo = x.options().dtype(at::kFloat);
+  std::vector<at::Tensor> out{at::empty({6, C}, fo), at::empty({C}, fo), at::empty({C}, fo), at::empty({C}, fo),
+                              at::empty({C}, fo)};
+  at::Tensor ws = at::empty({(int64_t)madnn_bn_partial_rows(M, (int)C) * 3 * C}, fo);
+  check(madnn_bn_bwd_dual_coef(dy.data_ptr(), x.data_ptr(), r.data_ptr(), mask.data_ptr<uint8_t>(), M, (int)C, optf(w),
+                               save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), optf(w_r),
+                               save_mean_r.data_ptr<float>(), save_invstd_r.data_ptr<float>(),
+                               out[1].data_ptr<float>(), out[2].data_ptr<float>(), out[3].data_ptr<float>(),
+                               out[4].data_ptr<float>(), out[0].data_ptr<float>(), ws.data_ptr<float>(),
+                               cur_stream(x)),
+        "bn_bwd_dual_coef");
+  return out;
+}
+
 // Training BatchNorm coefficients only (statistics pass unless `partial` is given, finalize with
 // the running-stat update): -> mean, invstd, scale, shift.  The apply is left to a consumer
 // kernel (K9's BatchNorm prologue).
@@ -713,37 +748,51 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_bwd_coef(const at::Tensor& dy,
 bool bn3_conv3_bwd_supported(int64_t c, int64_t c4) { return madnn_bn3_conv3_bwd_supported(c, c4) != 0; }
 
 // K9F: backward of relu(bn3(conv3(a2)) + idt) behind bn3's reduction (coef from bn_bwd_coef), a2 = relu(bn2(y2)):
-// -> (da2, bn2's backward partial sums [rows, 2, C], dW3 [4C, C] fp32 or bf16)
+// -> (da2, bn2's backward partial sums [rows, 2, C], dW3 [4C, C] fp32 or bf16).
+// Without y2 / scale2 / shift2 (all three or none): the same walk for a convolution with no BatchNorm of the
+// block in front of it (the downsample path: y3 = yd, coef = the residual BatchNorm's, w3 = W_ds, a2 = xf)
+// -> (dxf stored plainly, an empty partial, dW_ds)
 std::tuple<at::Tensor, at::Tensor, at::Tensor> bn3_conv3_bwd(const at::Tensor& dout, const at::Tensor& y3,
                                                              const at::Tensor& mask, const at::Tensor& coef,
                                                              const at::Tensor& w3, const at::Tensor& a2,
-                                                             const at::Tensor& y2, const at::Tensor& scale2,
-                                                             const at::Tensor& shift2, bool dw_bf16) {
+                                                             const c10::optional<at::Tensor>& y2,
+                                                             const c10::optional<at::Tensor>& scale2,
+                                                             const c10::optional<at::Tensor>& shift2, bool dw_bf16) {
   const int64_t c4 = y3.size(1), c = a2.size(1);
   const int64_t M = conv_rows(y3, c4, "y3");
   TORCH_CHECK(madnn_bn3_conv3_bwd_supported(c, c4), "bn3_conv3_bwd: unsupported channels ", c, " -> ", c4);
   TORCH_CHECK(M > 0, "bn3_conv3_bwd: empty input");
   TORCH_CHECK(conv_rows(dout, c4, "dout") == M && dout.dim() == y3.dim(), "bn3_conv3_bwd: dout layout");
   TORCH_CHECK(conv_rows(a2, c, "a2") == M && a2.dim() == y3.dim(), "bn3_conv3_bwd: a2 layout");
-  TORCH_CHECK(conv_rows(y2, c, "y2") == M && y2.dim() == y3.dim(), "bn3_conv3_bwd: y2 layout");
+  auto given = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); };
+  const bool bnb = given(y2);
+  TORCH_CHECK(given(scale2) == bnb && given(shift2) == bnb, "bn3_conv3_bwd: y2, scale2 and shift2 go together");
+  if (bnb) {
+    TORCH_CHECK(conv_rows(*y2, c, "y2") == M && y2->dim() == y3.dim(), "bn3_conv3_bwd: y2 layout");
+  }
   conv_check_w(w3, c4, c);
   TORCH_CHECK(mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() == M * c4 / 8,
               "bn3_conv3_bwd: ReLU bit mask over y3 required");
   TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * c4,
               "bn3_conv3_bwd: fp32 [3, 4C] coefficients");
-  TORCH_CHECK(scale2.numel() == c && shift2.numel() == c && scale2.scalar_type() == at::kFloat &&
-                  shift2.scalar_type() == at::kFloat && scale2.is_contiguous() && shift2.is_contiguous(),
-              "bn3_conv3_bwd: fp32 [C] scale / shift");
+  if (bnb) {
+    check_dev(*scale2, "scale2");
+    check_dev(*shift2, "shift2");
+    TORCH_CHECK(scale2->numel() == c && shift2->numel() == c && scale2->scalar_type() == at::kFloat &&
+                    shift2->scalar_type() == at::kFloat && scale2->is_contiguous() && shift2->is_contiguous(),
+                "bn3_conv3_bwd: fp32 [C] scale / shift");
+  }
   at::hip::HIPGuardMasqueradingAsCUDA guard(y3.device());
   auto fo = y3.options().dtype(at::kFloat);
   const int64_t groups = madnn_bn3_conv3_bwd_groups(M);
   at::Tensor da2 = conv_out_like(y3, c);
-  at::Tensor part = at::empty({groups, 2, c}, fo);
+  at::Tensor part = at::empty({bnb ? groups : 0, 2, c}, fo);
   at::Tensor slabs = at::empty({groups, c4, c}, fo);
   at::Tensor dw = at::empty({c4, c}, y3.options().dtype(dw_bf16 ? at::kBFloat16 : at::kFloat));
   check(madnn_bn3_conv3_bwd(dout.data_ptr(), y3.data_ptr(), mask.data_ptr<uint8_t>(), coef.data_ptr<float>(),
-                            w3.data_ptr(), a2.data_ptr(), y2.data_ptr(), scale2.data_ptr<float>(),
-                            shift2.data_ptr<float>(), da2.data_ptr(), part.data_ptr<float>(), slabs.data_ptr<float>(),
+                            w3.data_ptr(), a2.data_ptr(), bnb ? y2->data_ptr() : nullptr,
+                            bnb ? scale2->data_ptr<float>() : nullptr, bnb ? shift2->data_ptr<float>() : nullptr,
+                            da2.data_ptr(), bnb ? part.data_ptr<float>() : nullptr, slabs.data_ptr<float>(),
                             dw.data_ptr(), dw_bf16 ? 1 : 0, M, c, c4, cur_stream(y3)),
         "bn3_conv3_bwd");
   return {da2, part, dw};
@@ -1566,10 +1615,13 @@ TORCH_LIBRARY(madnn, m) {
   m.def(
       "bn_bwd_coef(Tensor dy, Tensor x, Tensor mask, Tensor? w, Tensor save_mean, Tensor save_invstd, Tensor scale, "
       "Tensor shift) -> (Tensor, Tensor, Tensor)");
+  m.def(
+      "bn_bwd_dual_coef(Tensor dy, Tensor x, Tensor r, Tensor mask, Tensor? w, Tensor save_mean, Tensor save_invstd, "
+      "Tensor? w_r, Tensor save_mean_r, Tensor save_invstd_r) -> Tensor[]");
   m.def("bn3_conv3_bwd_supported(int c, int c4) -> bool", &bn3_conv3_bwd_supported);
   m.def(
-      "bn3_conv3_bwd(Tensor dout, Tensor y3, Tensor mask, Tensor coef, Tensor w3, Tensor a2, Tensor y2, Tensor scale2, "
-      "Tensor shift2, bool dw_bf16) -> (Tensor, Tensor, Tensor)");
+      "bn3_conv3_bwd(Tensor dout, Tensor y3, Tensor mask, Tensor coef, Tensor w3, Tensor a2, Tensor? y2, "
+      "Tensor? scale2, Tensor? shift2, bool dw_bf16) -> (Tensor, Tensor, Tensor)");
   m.def(
       "bn_coef(Tensor x, Tensor? w, Tensor? b, Tensor(a!)? run_mean, Tensor(b!)? run_var, Tensor(c!)? nbt, "
       "float momentum, float eps, Tensor? partial=None) -> Tensor[]");
@@ -1653,6 +1705,7 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("conv1x1_dgrad", conv1x1_dgrad);
   m.impl("conv1x1_wgrad", conv1x1_wgrad);
   m.impl("bn_bwd_coef", bn_bwd_coef);
+  m.impl("bn_bwd_dual_coef", bn_bwd_dual_coef);
   m.impl("bn3_conv3_bwd", bn3_conv3_bwd);
   m.impl("stem_fwd", stem_fwd);
   m.impl("stem_wgrad", stem_wgrad);

@@ -728,13 +728,15 @@ hipError_t madnn_bn_fwd_dual(const void* x, const void* r, void* y, unsigned cha
   return hipGetLastError();
 }
 
-// Backward of madnn_bn_fwd_dual: one reduction pass (sum g, sum g*x, sum g*r), two finalizes, one
-// apply pass writing dx and dr.  workspace: bn_partial_rows(M, C) * 3 * C floats; coef: 6 * C.
-hipError_t madnn_bn_bwd_dual(const void* dy, const void* x, const void* r, const unsigned char* mask, void* dx,
-                             void* dr, int64_t M, int C, const float* w, const float* save_mean,
-                             const float* save_invstd, const float* w_r, const float* save_mean_r,
-                             const float* save_invstd_r, float* dw, float* db, float* dw_r, float* db_r, float* coef,
-                             float* workspace, hipStream_t stream) {
+// The dual backward's reduction and its two finalizes without the apply pass: dw / db of both BatchNorms and
+// coef = ca | cb | cc (dx = ca g + cb x + cc) followed by the residual BatchNorm's ca | cb | cc over r
+// ([6][C]), for consumers that apply them themselves (K9F on both convolutions of a downsample block).
+// workspace: bn_partial_rows(M, C) * 3 * C floats.
+hipError_t madnn_bn_bwd_dual_coef(const void* dy, const void* x, const void* r, const unsigned char* mask, int64_t M,
+                                  int C, const float* w, const float* save_mean, const float* save_invstd,
+                                  const float* w_r, const float* save_mean_r, const float* save_invstd_r, float* dw,
+                                  float* db, float* dw_r, float* db_r, float* coef, float* workspace,
+                                  hipStream_t stream) {
   using namespace madnn;
   if (!madnn_bn_supported(C) || mask == nullptr) return hipErrorInvalidValue;
   if (M <= 0) return hipSuccess;
@@ -750,7 +752,21 @@ hipError_t madnn_bn_bwd_dual(const void* dy, const void* x, const void* r, const
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(32 * kFinSlices), 0, stream, workspace, G, C,
                      3 * C, 2 * C, M, w_r, save_mean_r, save_invstd_r, dw_r, db_r, coef + 3 * C, coef + 4 * C,
                      coef + 5 * C);
-  MADNN_HIP_CHECK(hipGetLastError());
+  return hipGetLastError();
+}
+
+// Backward of madnn_bn_fwd_dual: one reduction pass (sum g, sum g*x, sum g*r), two finalizes, one
+// apply pass writing dx and dr.  workspace: bn_partial_rows(M, C) * 3 * C floats; coef: 6 * C.
+hipError_t madnn_bn_bwd_dual(const void* dy, const void* x, const void* r, const unsigned char* mask, void* dx,
+                             void* dr, int64_t M, int C, const float* w, const float* save_mean,
+                             const float* save_invstd, const float* w_r, const float* save_mean_r,
+                             const float* save_invstd_r, float* dw, float* db, float* dw_r, float* db_r, float* coef,
+                             float* workspace, hipStream_t stream) {
+  using namespace madnn;
+  if (!madnn_bn_supported(C) || mask == nullptr) return hipErrorInvalidValue;
+  if (M <= 0) return hipSuccess;
+  MADNN_HIP_CHECK(madnn_bn_bwd_dual_coef(dy, x, r, mask, M, C, w, save_mean, save_invstd, w_r, save_mean_r,
+                                         save_invstd_r, dw, db, dw_r, db_r, coef, workspace, stream));
   const int64_t total = M * C;
   const int grid = stream_grid(total, 256 * 8, bn_tune().wg_per_cu * kNumCU);
   hipLaunchKernelGGL((bn_bwd_apply_kernel<kBF16, true, true, true>), dim3(grid), dim3(256), 0, stream, dy, x, mask,

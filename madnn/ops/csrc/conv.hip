@@ -418,26 +418,33 @@ inline void wgrad_split(int64_t M, int64_t cin, int64_t cout, int& bi, int& bj, 
 // 256 x 64 dW3 accumulators in registers (64 per lane); each workgroup stores one fp32 slab and
 // split_reduce_kernel sums the slabs in workgroup order (deterministic).
 // LDS: W3 32 KiB + dy3 2 x 16 KiB + a2 16 KiB = 80 KiB: two workgroups per CU.
+// The layer-1 downsample block, relu(bn3(conv3(a2)) + bn_ds(conv_ds(xf))), runs the kernel twice behind the
+// dual reduction: once as above, and once with (yd, bn_ds's coefficients, W_ds, xf) in the place of
+// (y3, bn3's, W3, a2) and without the BNB epilogue (template parameter BNB below).
 constexpr int kFC = 64, kFC4 = 256, kFBM = 128;
 constexpr int kFW = kFC4 * kFC, kFT = kFBM * 64;  // LDS elements: W3 image, one [128][64] tile
 
 struct FusedArgs {
   const uint16_t* dout;       // [M][4C]
-  const uint16_t* y3;         // [M][4C] bn3's input
-  const unsigned char* mask;  // bn3's ReLU bit mask over [M][4C], 8 per byte
-  const float* coef;          // bn3's backward coefficients ca | cb | cc, [3][4C]
-  const uint16_t* w3;         // [4C][C]
-  const uint16_t* a2;         // [M][C] relu(bn2(y2))
-  const uint16_t* y2;         // [M][C]
-  const float* sc2;           // bn2's forward scale / shift
+  const uint16_t* y;          // [M][4C] the BatchNorm's input: y3 (bn3) or yd (the downsample BatchNorm)
+  const unsigned char* mask;  // the block's ReLU bit mask over [M][4C], 8 per byte
+  const float* coef;          // that BatchNorm's backward coefficients ca | cb | cc, [3][4C]
+  const uint16_t* w;          // [4C][C]: W3 or W_ds
+  const uint16_t* a;          // [M][C] the convolution's input: a2 = relu(bn2(y2)), or xf
+  const uint16_t* y2;         // [M][C]                      (BNB only)
+  const float* sc2;           // bn2's forward scale / shift (BNB only)
   const float* sh2;
-  uint16_t* da2;              // [M][C]
-  float* partial;             // [grid][2][C] bn2's backward sums
+  uint16_t* da;               // [M][C] the data gradient
+  float* partial;             // [grid][2][C] bn2's backward sums (BNB only)
   float* slabs;               // [grid][4C][C]
   int64_t M;
   int m_tiles;
 };
 
+// BNB: the data gradient is d relu(bn2(y2)) and the epilogue also takes bn2's backward sums over it (conv3).
+// Without it the data gradient is stored plainly: no y2 / sc2 / sh2 reads, no sums, no partial row (the
+// downsample convolution, whose input xf has no BatchNorm of this block in front of it).
+template <bool BNB>
 __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedArgs p) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[kFW + 3 * kFT];
   uint16_t* const wt = smem;             // [256 co][64 ci], swz<64>
@@ -452,13 +459,13 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
     Stage<false, kFBM> sw;
 #pragma unroll
     for (int h = 0; h < kFC4 / kFBM; ++h) {
-      sw.load(p.w3, kFC, h * kFBM, kFC4, 0, kFC, tid);
+      sw.load(p.w, kFC, h * kFBM, kFC4, 0, kFC, tid);
       sw.store(wt + h * kFT, tid);
     }
   }
-  float ssum[8], ssq[8];
+  float ssum[BNB ? 8 : 1], ssq[BNB ? 8 : 1];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) ssum[e] = ssq[e] = 0.f;
+  for (int e = 0; e < (BNB ? 8 : 1); ++e) ssum[e] = ssq[e] = 0.f;
   f32x16 accw[kFC4 / 64], accd[2];
 #pragma unroll
   for (int q = 0; q < kFC4 / 64; ++q) accw[q] = zero16();
@@ -482,7 +489,7 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
   auto load_step = [&](int tile, int q) {
     const int64_t m0 = (int64_t)tile * kFBM;
     const char* bd = reinterpret_cast<const char*>(p.dout + m0 * kFC4 + q * 64);
-    const char* by = reinterpret_cast<const char*>(p.y3 + m0 * kFC4 + q * 64);
+    const char* by = reinterpret_cast<const char*>(p.y + m0 * kFC4 + q * 64);
     const unsigned char* bm = p.mask + m0 * (kFC4 / 8) + q * 8;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -494,7 +501,7 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
     }
   };
   auto load_a2 = [&](int tile) {
-    const char* ba = reinterpret_cast<const char*>(p.a2 + (int64_t)tile * kFBM * kFC);
+    const char* ba = reinterpret_cast<const char*>(p.a + (int64_t)tile * kFBM * kFC);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       sa[i] = *reinterpret_cast<const u32x4*>(ba + opaque(((unsigned)row_of(tile, i) * kFC + 8 * c8) * 2u));
@@ -604,36 +611,49 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
         __syncthreads();
         // full-row 16-B stores of da2, and bn2's backward sums over what is stored (BNB); bn2's scale and
         // shift are reloaded per tile (cache hits) instead of held in 16 registers across the walk
-        float bs[8], bh[8];
+        if constexpr (BNB) {
+          float bs[8], bh[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          bs[e] = p.sc2[8 * c8 + e];
-          bh[e] = p.sh2[8 * c8 + e];
-        }
-        const int64_t m0 = (int64_t)tile * kFBM;
-        const int valid = (int)min((int64_t)kFBM, p.M - m0);
-        char* bo = reinterpret_cast<char*>(p.da2 + m0 * kFC);
-        const char* by2 = reinterpret_cast<const char*>(p.y2 + m0 * kFC);
+          for (int e = 0; e < 8; ++e) {
+            bs[e] = p.sc2[8 * c8 + e];
+            bh[e] = p.sh2[8 * c8 + e];
+          }
+          const int64_t m0 = (int64_t)tile * kFBM;
+          const int valid = (int)min((int64_t)kFBM, p.M - m0);
+          char* bo = reinterpret_cast<char*>(p.da + m0 * kFC);
+          const char* by2 = reinterpret_cast<const char*>(p.y2 + m0 * kFC);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int r = r8 + 32 * u;
-          if (r < valid) {
-            const unsigned off = opaque(((unsigned)r * kFC + 8 * c8) * 2u);
-            const u32x4 v = *reinterpret_cast<const u32x4*>(ot + opaque((unsigned)out_off(r8, c8)) + 4096 * u);
-            *reinterpret_cast<u32x4*>(bo + off) = v;
-            const u32x4 yv = *reinterpret_cast<const u32x4*>(by2 + off);
+          for (int u = 0; u < 4; ++u) {
+            const int r = r8 + 32 * u;
+            if (r < valid) {
+              const unsigned off = opaque(((unsigned)r * kFC + 8 * c8) * 2u);
+              const u32x4 v = *reinterpret_cast<const u32x4*>(ot + opaque((unsigned)out_off(r8, c8)) + 4096 * u);
+              *reinterpret_cast<u32x4*>(bo + off) = v;
+              const u32x4 yv = *reinterpret_cast<const u32x4*>(by2 + off);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
+              for (int e = 0; e < 4; ++e) {
 #pragma unroll
-              for (int hf = 0; hf < 2; ++hf) {
-                const int k = 2 * e + hf;
-                const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
-                const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
-                const float gm = yy * bs[k] + bh[k] > 0.f ? g : 0.f;
-                ssum[k] += gm;
-                ssq[k] += gm * yy;
+                for (int hf = 0; hf < 2; ++hf) {
+                  const int k = 2 * e + hf;
+                  const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
+                  const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
+                  const float gm = yy * bs[k] + bh[k] > 0.f ? g : 0.f;
+                  ssum[k] += gm;
+                  ssq[k] += gm * yy;
+                }
               }
             }
+          }
+        } else {
+          const int64_t m0 = (int64_t)tile * kFBM;
+          const int valid = (int)min((int64_t)kFBM, p.M - m0);
+          char* bo = reinterpret_cast<char*>(p.da + m0 * kFC);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int r = r8 + 32 * u;
+            if (r < valid)
+              *reinterpret_cast<u32x4*>(bo + opaque(((unsigned)r * kFC + 8 * c8) * 2u)) =
+                  *reinterpret_cast<const u32x4*>(ot + opaque((unsigned)out_off(r8, c8)) + 4096 * u);
           }
         }
       }
@@ -653,21 +673,23 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       slab[(q * 64 + (w2 >> 1) * 32 + acc_row(r, h2)) * kFC + (w2 & 1) * 32 + col2] = accw[q][r];
-  // bn2's partial row: sum the 32 row groups through LDS
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(dyt);  // [32][2][64]
-  const int rg = t2 >> 3, cg = t2 & 7;
+  if constexpr (BNB) {
+    // bn2's partial row: sum the 32 row groups through LDS
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(dyt);  // [32][2][64]
+    const int rg = t2 >> 3, cg = t2 & 7;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    red[(rg * 2) * kFC + 8 * cg + e] = ssum[e];
-    red[(rg * 2 + 1) * kFC + 8 * cg + e] = ssq[e];
-  }
-  __syncthreads();
-  if (t2 < 2 * kFC) {
-    const int which = t2 / kFC, ii = t2 % kFC;
-    float v = 0.f;
-    for (int g = 0; g < 32; ++g) v += red[(g * 2 + which) * kFC + ii];
-    p.partial[((int64_t)blockIdx.x * 2 + which) * kFC + ii] = v;
+    for (int e = 0; e < 8; ++e) {
+      red[(rg * 2) * kFC + 8 * cg + e] = ssum[e];
+      red[(rg * 2 + 1) * kFC + 8 * cg + e] = ssq[e];
+    }
+    __syncthreads();
+    if (t2 < 2 * kFC) {
+      const int which = t2 / kFC, ii = t2 % kFC;
+      float v = 0.f;
+      for (int g = 0; g < 32; ++g) v += red[(g * 2 + which) * kFC + ii];
+      p.partial[((int64_t)blockIdx.x * 2 + which) * kFC + ii] = v;
+    }
   }
 }
 
@@ -834,30 +856,39 @@ int madnn_bn3_conv3_bwd_supported(int64_t c, int64_t c4) { return (c == kFC && c
 // workgroups = bn2 partial rows ([rows][2][C]) = dW3 slabs ([rows][4C][C] fp32 of workspace)
 int madnn_bn3_conv3_bwd_groups(int64_t M) { return M > 0 ? fused_groups(M) : 0; }
 
-// coef: bn3's ca | cb | cc ([3][4C], bn_bwd_finalize_kernel); partial / slabs: madnn_bn3_conv3_bwd_groups rows;
+// K9F launch.  y / coef / w / a: the BatchNorm input, its ca | cb | cc ([3][4C], bn_bwd_finalize_kernel), the
+// weight and the convolution input -- bn3's set (y3, W3, a2) or the downsample path's (yd, W_ds, xf).
+// y2 / sc2 / sh2 / partial all given: da is d relu(bn2(y2)) and partial gets bn2's backward sums (BNB); all
+// null: da is stored plainly.  partial / slabs: madnn_bn3_conv3_bwd_groups rows;
 // dw: [4C][C] fp32 or (dw_bf16) bf16, the slabs summed in workgroup order
-hipError_t madnn_bn3_conv3_bwd(const void* dout, const void* y3, const unsigned char* mask, const float* coef,
-                               const void* w3, const void* a2, const void* y2, const float* sc2, const float* sh2,
-                               void* da2, float* partial, float* slabs, void* dw, int dw_bf16, int64_t M, int64_t c,
+hipError_t madnn_bn3_conv3_bwd(const void* dout, const void* y, const unsigned char* mask, const float* coef,
+                               const void* w, const void* a, const void* y2, const float* sc2, const float* sh2,
+                               void* da, float* partial, float* slabs, void* dw, int dw_bf16, int64_t M, int64_t c,
                                int64_t c4, hipStream_t s) {
   if (!madnn_bn3_conv3_bwd_supported(c, c4) || M <= 0) return hipErrorInvalidValue;
+  const bool bnb = y2 != nullptr;
+  if (bnb != (sc2 != nullptr) || bnb != (sh2 != nullptr) || bnb != (partial != nullptr)) return hipErrorInvalidValue;
   FusedArgs p{};
   p.dout = static_cast<const uint16_t*>(dout);
-  p.y3 = static_cast<const uint16_t*>(y3);
+  p.y = static_cast<const uint16_t*>(y);
   p.mask = mask;
   p.coef = coef;
-  p.w3 = static_cast<const uint16_t*>(w3);
-  p.a2 = static_cast<const uint16_t*>(a2);
+  p.w = static_cast<const uint16_t*>(w);
+  p.a = static_cast<const uint16_t*>(a);
   p.y2 = static_cast<const uint16_t*>(y2);
   p.sc2 = sc2;
   p.sh2 = sh2;
-  p.da2 = static_cast<uint16_t*>(da2);
+  p.da = static_cast<uint16_t*>(da);
   p.partial = partial;
   p.slabs = slabs;
   p.M = M;
   p.m_tiles = (int)((M + kFBM - 1) / kFBM);
   const int grid = fused_groups(M);
-  hipLaunchKernelGGL(bn3_conv3_bwd_kernel, dim3(grid), dim3(kThreads), 0, s, p);
+  if (bnb) {
+    hipLaunchKernelGGL(bn3_conv3_bwd_kernel<true>, dim3(grid), dim3(kThreads), 0, s, p);
+  } else {
+    hipLaunchKernelGGL(bn3_conv3_bwd_kernel<false>, dim3(grid), dim3(kThreads), 0, s, p);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int64_t n = kFW;
