@@ -22,7 +22,8 @@ convolutions prefer.
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Type
+from collections import namedtuple
+from typing import List, Type
 
 import torch
 from torch import nn
@@ -32,8 +33,8 @@ from ..nn.norm import FusedBatchNorm2d as BN
 from ..nn.norm import FusedGlobalAvgPool2d, FusedMaxPool2d
 from ..ops import (batch_norm_add_bn_relu, bn2_conv3_bn3_add_bn_relu, bn2_conv3_bn3_add_bn_relu_supported,
                    bn2_conv3_bn3_add_relu, bn2_conv3_bn3_supported, bn_relu_conv1x1,
-                   bn_relu_conv1x1_epi_supported, bn_relu_conv3x3, conv1x1_route,
-                   bn_relu_conv3x3_supported, bn_relu_maxpool, bn_relu_maxpool_supported)
+                   bn_relu_conv1x1_epi_supported, bn_relu_conv3x3, bn_relu_conv3x3_supported, bn_relu_maxpool,
+                   bn_relu_maxpool_supported, conv1x1_route, defer_res_mask)
 
 # A/B knob: sum the downsample path's input gradient inside conv1's data grad (1) or by autograd (0)
 _FORK_DS = os.environ.get("MADNN_FORK_DOWNSAMPLE", "1") != "0"
@@ -42,6 +43,12 @@ _DUAL_BN = os.environ.get("MADNN_DUAL_BN", "1") != "0"
 # A/B knob: the stride-2 1x1 downsample convolution as a stride-1 1x1 on conv1's compact subsample
 # of the block input (1) or as a stride-2 library convolution on the full input (0)
 _DS_SUB = os.environ.get("MADNN_DS_SUB", "1") != "0"
+
+
+# Bottleneck.forward's routes (Bottleneck._route); each is explained where forward issues it
+ROUTES = (IDENTITY_K9F, IDENTITY, DUAL_SUB, DUAL_K9F, DUAL, FORK_DS, PLAIN_DS) = (
+    "identity+k9f", "identity", "dual+sub", "dual+k9f", "dual", "fork-ds", "plain-ds")
+_Fused = namedtuple("_Fused", "bn1_conv2 bn2_conv3 bn3 dual")
 
 
 def conv3x3(cin, cout, stride=1, groups=1, dilation=1):
@@ -86,88 +93,112 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        if self.downsample is None:
-            # K9: BN statistics from the GEMM epilogue; the identity path's gradient is added
-            # inside conv1's data-grad kernel (no separate residual-gradient add)
-            y, st, idt = self.conv1(x, stats=True, fork=True)
-            if isinstance(idt, torch.Tensor) and isinstance(self.bn3, BN) and self.conv1._k9(x) \
-                    and conv1x1_route(x.size(1), self.conv1.weight.size(0))[1] == "k9":
+        fused = self._fused()
+        route = self._route(x, fused)
+        ds = self.downsample
+        # head: conv1 on K9 (BN statistics from the GEMM epilogue) and what joins the tail from the side
+        if route in (IDENTITY_K9F, IDENTITY):
+            # the identity path's gradient is added inside conv1's data-grad kernel (no separate
+            # residual-gradient add)
+            y, st, side = self.conv1(x, stats=True, fork=True)
+            if route == IDENTITY_K9F:
                 # idt's only consumer is bn3 and its gradient is summed inside K9's data grad: that
                 # kernel applies bn3's ReLU mask itself (ops._BNFn deferred mask)
-                idt._madnn_defer_mask = True
-        elif _FORK_DS:
-            # the downsample path's input gradient is likewise summed inside conv1's data grad
-            dual = self._dual_bn()
-            sub = dual and _DS_SUB and isinstance(x, torch.Tensor) and self.downsample[0].subsampled_ok()
-            y, st, xf = self.conv1(x, stats=True, fork=2 if sub else True)
-            if dual:
-                # relu(bn3(conv3) + bn_ds(conv_ds)): the downsample BN is applied inside bn3's
-                # passes (forward and backward), its normalised output never written to HBM.
-                # sub: conv1 hands over the compact x[:, :, ::2, ::2] and the stride-2 downsample
-                # runs as a stride-1 1x1 on it (K9, BN statistics from its epilogue); its compact
-                # input gradient is added into conv1's data grad at the even pixels
-                ds, bn_ds = self.downsample
-                if not sub and self._k9f_dual(y, xf):
-                    # layer 1's downsample block: K9F once per convolution; the downsample convolution is
-                    # issued inside the function, and neither dy3 nor dyd is written in the backward
-                    y, st = self._bn1_conv2(y, st)
-                    if self._k9f_dual(y, xf):
-                        return bn2_conv3_bn3_add_bn_relu(y, self.bn2, self.conv3.weight, self.bn3, xf, ds.weight,
-                                                         bn_ds, stats_in=st)
-                    yd, std = ds(xf, stats=True)
-                    y, st = self._bn2_conv3(y, st)
-                    return batch_norm_add_bn_relu(y, yd, self.bn3, bn_ds, st, std)
-                yd, std = (self.downsample[0].forward_subsampled(xf, stats=True) if sub
-                           else self.downsample[0](xf, stats=True))
-                y, st = self._bn1_conv2(y, st)
-                y, st = self._bn2_conv3(y, st)
-                return batch_norm_add_bn_relu(y, yd, self.bn3, self.downsample[1], st, std)
-            idt = self.downsample(xf)
-        else:
-            idt = self.downsample(x)
+                defer_res_mask(side)
+        elif route == PLAIN_DS:
+            side = ds(x)
             y, st = self.conv1(x, stats=True)
-        y, st = self._bn1_conv2(y, st)   # K13 at stride 1: BN statistics from the epilogue
-        if self.downsample is None and isinstance(self.bn2, BN) and isinstance(self.bn3, BN) \
-                and isinstance(self.conv3, FusedConv2d) and isinstance(y, torch.Tensor) and self.conv3._k9(y) \
-                and bn2_conv3_bn3_supported(y, self.bn2, self.conv3.weight, self.bn3, idt):
+        else:
+            # the downsample path's input gradient is likewise summed inside conv1's data grad.
+            # DUAL_SUB: conv1 hands over the compact x[:, :, ::2, ::2] and the stride-2 downsample
+            # runs as a stride-1 1x1 on it (K9, BN statistics from its epilogue); its compact
+            # input gradient is added into conv1's data grad at the even pixels
+            y, st, xf = self.conv1(x, stats=True, fork=2 if route == DUAL_SUB else True)
+            if route == DUAL_K9F and not self._k9f_dual(y, xf):
+                route = DUAL
+            if route == FORK_DS:
+                side = ds(xf)
+            elif route == DUAL_SUB:
+                side = ds[0].forward_subsampled(xf, stats=True)
+            elif route == DUAL:
+                side = ds[0](xf, stats=True)
+        y1 = y   # DUAL_K9F was confirmed on conv1's output
+        y, st = self._bn1_conv2(y, st, fused)   # K13 at stride 1: BN statistics from the epilogue
+        # tail: conv3, bn3 and the residual add
+        if route == IDENTITY_K9F and fused.bn2_conv3 and isinstance(y, torch.Tensor) and self.conv3._k9(y) \
+                and bn2_conv3_bn3_supported(y, self.bn2, self.conv3.weight, self.bn3, side):
             # layer 1's identity blocks: one backward kernel for bn3's apply and conv3's two gradients (K9F)
-            return bn2_conv3_bn3_add_relu(y, self.bn2, self.conv3.weight, self.bn3, idt, stats_in=st)
-        y, st = self._bn2_conv3(y, st)
-        return self.bn3(y, residual=idt, relu=True, stats=st)   # relu(bn3 + idt): one kernel
+            return bn2_conv3_bn3_add_relu(y, self.bn2, self.conv3.weight, self.bn3, side, stats_in=st)
+        if route == DUAL_K9F:
+            # layer 1's downsample block: K9F once per convolution; the downsample convolution is
+            # issued inside the function, and neither dy3 nor dyd is written in the backward
+            if isinstance(y, torch.Tensor) and y.requires_grad \
+                    and (y.shape, y.stride(), y.dtype) == (y1.shape, y1.stride(), y1.dtype):   # conv2 kept these
+                return bn2_conv3_bn3_add_bn_relu(y, self.bn2, self.conv3.weight, self.bn3, xf, ds[0].weight,
+                                                 ds[1], stats_in=st)
+            route, side = DUAL, ds[0](xf, stats=True)
+        y, st = self._bn2_conv3(y, st, fused)
+        if route in (DUAL_SUB, DUAL):
+            # relu(bn3(conv3) + bn_ds(conv_ds)): the downsample BN is applied inside bn3's
+            # passes (forward and backward), its normalised output never written to HBM
+            return batch_norm_add_bn_relu(y, side[0], self.bn3, ds[1], st, side[1])
+        return self.bn3(y, residual=side, relu=True, stats=st)   # relu(bn3 + idt): one kernel
 
-    def _bn1_conv2(self, y, st):
+    def _fused(self) -> "_Fused":
+        """Which of the block's own modules are the fused kinds (a model surgery may have swapped some)."""
+        ds = self.downsample
+        return _Fused(bn1_conv2=isinstance(self.bn1, BN) and isinstance(self.conv2, FusedConv2d),
+                      bn2_conv3=isinstance(self.bn2, BN) and isinstance(self.conv3, FusedConv2d),
+                      bn3=isinstance(self.bn3, BN),
+                      dual=(isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], FusedConv2d)
+                            and isinstance(ds[1], BN) and isinstance(self.bn3, BN)))
+
+    def _dual_bn(self) -> bool:
+        return _DUAL_BN and self._fused().dual
+
+    def _route(self, x, fused: "_Fused") -> str:
+        """Which of ROUTES this block takes for ``x``, decided before any kernel is issued.  A K9F route is
+        confirmed once the tensors its node takes exist (IDENTITY_K9F after conv2, DUAL_K9F after conv1,
+        :meth:`_k9f_dual`) and continues as IDENTITY (the ReLU mask still deferred) / DUAL otherwise."""
+        ds, tensor = self.downsample, isinstance(x, torch.Tensor)
+        if ds is None:
+            defer = (tensor and fused.bn3 and self.conv1._k9(x)
+                     and conv1x1_route(x.size(1), self.conv1.weight.size(0))[1] == "k9")
+            return IDENTITY_K9F if defer else IDENTITY
+        if not _FORK_DS:
+            return PLAIN_DS
+        if not (_DUAL_BN and fused.dual):
+            return FORK_DS
+        if _DS_SUB and tensor and ds[0].subsampled_ok():
+            return DUAL_SUB
+        return DUAL_K9F if tensor and fused.bn2_conv3 and self.conv2.stride == (1, 1) else DUAL
+
+    def _bn1_conv2(self, y, st, fused):
         """conv2(relu(bn1(y))): with conv2 on K13, bn1's backward reduction is taken in conv2's
         data-grad epilogue (ops.bn_relu_conv3x3); the stride-2 conv2s take the module path (K13's stride-2
         forward on small maps, the library otherwise)."""
-        if isinstance(y, torch.Tensor) and isinstance(self.bn1, BN) and isinstance(self.conv2, FusedConv2d) \
-                and self.conv2._k13(y) \
+        if fused.bn1_conv2 and isinstance(y, torch.Tensor) and self.conv2._k13(y) \
                 and bn_relu_conv3x3_supported(y, self.bn1, self.conv2.weight):
-            return bn_relu_conv3x3(y, self.bn1, self.conv2.weight, stats_in=st, stats=True)
+            return bn_relu_conv3x3(y, self.bn1, self.conv2.weight, stats_in=st, stats=True, checked=True)
         out = self.bn1(y, relu=True, stats=st)
         return self.conv2(out, stats=True)
 
-    def _bn2_conv3(self, y, st):
+    def _bn2_conv3(self, y, st, fused):
         """conv3(relu(bn2(y))): when conv3's data grad runs on K9, bn2's backward reduction is taken
         in that kernel's epilogue."""
-        if isinstance(y, torch.Tensor) and isinstance(self.bn2, BN) and isinstance(self.conv3, FusedConv2d) \
-                and self.conv3._k9(y) and bn_relu_conv1x1_epi_supported(y, self.bn2, self.conv3.weight):
-            return bn_relu_conv1x1(y, self.bn2, self.conv3.weight, stats_in=st, stats=True)
+        if fused.bn2_conv3 and isinstance(y, torch.Tensor) and self.conv3._k9(y) \
+                and bn_relu_conv1x1_epi_supported(y, self.bn2, self.conv3.weight):
+            return bn_relu_conv1x1(y, self.bn2, self.conv3.weight, stats_in=st, stats=True, checked=True)
         out = self.bn2(y, relu=True, stats=st)
         return self.conv3(out, stats=True)
 
-    def _k9f_dual(self, y, xf) -> bool:
-        """K9F on conv3 and on a stride-1 downsample convolution (ops.bn2_conv3_bn3_add_bn_relu), asked with
-        conv1's output (conv2 at stride 1 keeps its shape) and again with conv2's."""
+    def _k9f_dual(self, y1, xf) -> bool:
+        """DUAL_K9F's confirmation, asked once with conv1's output: conv2 at stride 1 keeps its shape, and
+        what it can change (layout, dtype, requires_grad) is compared after it."""
         ds = self.downsample
-        return (isinstance(y, torch.Tensor) and isinstance(xf, torch.Tensor) and isinstance(self.bn2, BN)
-                and isinstance(self.conv3, FusedConv2d) and self.conv2.stride == (1, 1) and self.conv3._k9(y)
+        return (isinstance(y1, torch.Tensor) and isinstance(xf, torch.Tensor) and self.conv3._k9(y1)
                 and ds[0]._k9(xf) and bn2_conv3_bn3_add_bn_relu_supported(
-                    y, self.bn2, self.conv3.weight, self.bn3, xf, ds[0].weight, ds[1]))
-
-    def _dual_bn(self) -> bool:
-        ds = self.downsample
-        return (_DUAL_BN and isinstance(ds, nn.Sequential) and len(ds) == 2
-                and isinstance(ds[0], FusedConv2d) and isinstance(ds[1], BN) and isinstance(self.bn3, BN))
+                    y1, self.bn2, self.conv3.weight, self.bn3, xf, ds[0].weight, ds[1]))
 
 
 class ResNet(nn.Module):

@@ -293,7 +293,7 @@ class _BNFn(torch.autograd.Function):
         # is summed inside a K9 data grad (Bottleneck marks it): hand that kernel dy and the ReLU bit
         # mask instead of writing the masked copy of dy (one activation-sized write less)
         ctx.defer = (DEFER_RES_MASK and relu and residual is not None and mask.numel() > 0
-                     and getattr(residual, "_madnn_defer_mask", False))
+                     and _res_mask_deferred(residual))
         return y
 
     @staticmethod
@@ -311,6 +311,28 @@ class _BNFn(torch.autograd.Function):
 
 
 DEFER_RES_MASK = os.environ.get("MADNN_DEFER_RES_MASK", "1") != "0"  # A/B switch (see _BNFn.forward)
+
+
+def defer_res_mask(idt: torch.Tensor) -> None:
+    """Mark ``idt`` as a block's identity whose only consumer is the block's last BatchNorm and whose
+    gradient is summed inside a K9 data grad: that kernel applies the BatchNorm's ReLU mask itself."""
+    idt._madnn_defer_mask = True
+
+
+def _res_mask_deferred(idt: torch.Tensor) -> bool:
+    return getattr(idt, "_madnn_defer_mask", False)
+
+
+def _bn_trainable(m) -> bool:
+    """A BatchNorm module the fused nodes take: training, with running statistics and an fp32 affine."""
+    return (m.training and m.track_running_stats and m.affine and m.momentum is not None
+            and m.weight.dtype == torch.float32)
+
+
+def _bn_fwd_train(x, residual, weight, bias, bn, relu, stats):
+    """``bn_fwd`` for the training module ``bn`` (``weight`` / ``bias`` as the node's ``apply`` received them)."""
+    return torch.ops.madnn.bn_fwd(x, residual, weight, bias, bn.running_mean, bn.running_var,
+                                  bn.num_batches_tracked, True, float(bn.momentum), float(bn.eps), bool(relu), stats)
 
 
 def _apply_bit_mask(t: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -388,13 +410,9 @@ class _BNDualFn(torch.autograd.Function):
 
 def batch_norm_dual_supported(x: torch.Tensor, r: torch.Tensor, bn, bn_r) -> bool:
     """Shapes/modes :func:`batch_norm_add_bn_relu` runs as one fused kernel pair."""
-    def ok(m):
-        return (m.training and m.track_running_stats and m.affine and m.momentum is not None
-                and m.weight.dtype == torch.float32)
-    if not (isinstance(x, torch.Tensor) and isinstance(r, torch.Tensor)):   # e.g. fx tracing proxies
-        return False
-    return (x.dtype == torch.bfloat16 and bn_supported(x, bn.weight) and r.shape == x.shape
-            and r.dtype == x.dtype and r.stride() == x.stride() and ok(bn) and ok(bn_r))
+    return (isinstance(x, torch.Tensor) and isinstance(r, torch.Tensor)   # not e.g. fx tracing proxies
+            and x.dtype == torch.bfloat16 and bn_supported(x, bn.weight) and r.shape == x.shape
+            and r.dtype == x.dtype and r.stride() == x.stride() and _bn_trainable(bn) and _bn_trainable(bn_r))
 
 
 def batch_norm_add_bn_relu(x, r, bn, bn_r, stats=None, stats_r=None):
@@ -742,6 +760,27 @@ _K9_WGRAD = os.environ.get("MADNN_K9_WGRAD", "miopen")  # "k9" | "miopen" (A/B r
 _K9_DGRAD = os.environ.get("MADNN_K9_DGRAD", "narrow")  # "wide" | "narrow" (A/B runs)
 
 
+def _routed_conv1x1_fwd(fwd: str, x: torch.Tensor, w: torch.Tensor, stats: bool):
+    """``(y, part)`` on K9 or the library (then an empty ``part``), as :func:`conv1x1_route` chose."""
+    if fwd == "k9":
+        return torch.ops.madnn.conv1x1_fwd(x, w, bool(stats))
+    y = F.conv2d(x, w) if x.dim() == 4 else torch.mm(x, w.reshape(w.size(0), -1).t())
+    return y, x.new_empty((0, 2, w.size(0)), dtype=torch.float32)
+
+
+def _routed_conv1x1_wgrad(wgrad: str, dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    return _k9_wgrad(dy, x, w) if wgrad == "k9" else _conv1x1_wgrad_lib(dy, x, w)
+
+
+def _with_stats(out: torch.Tensor, part: torch.Tensor, stats: bool):
+    return (out, part if part.numel() else None) if stats else out
+
+
+def _like(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """``g`` in ``y``'s dtype and strides (a copy only if it is not already)."""
+    return g if g.dtype == y.dtype and g.stride() == y.stride() else torch.empty_like(y).copy_(g)
+
+
 class _Conv1x1Fn(torch.autograd.Function):
     """Stride-1 1x1 convolution on NHWC bf16 (see :func:`conv1x1_route`).  With ``fork`` the
     input is also returned (as the block's identity path); its gradient is then accumulated
@@ -754,11 +793,7 @@ class _Conv1x1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, stats, fork):
         fwd, dgrad, wgrad = conv1x1_route(x.size(1), w.size(0))
-        if fwd == "k9":
-            y, part = torch.ops.madnn.conv1x1_fwd(x, w, bool(stats))
-        else:
-            y = torch.nn.functional.conv2d(x, w) if x.dim() == 4 else torch.mm(x, w.reshape(w.size(0), -1).t())
-            part = x.new_empty((0, 2, w.size(0)), dtype=torch.float32)
+        y, part = _routed_conv1x1_fwd(fwd, x, w, stats)
         ctx.save_for_backward(x, w)
         ctx.route = (dgrad, wgrad)
         ctx.fork = fork
@@ -803,10 +838,7 @@ class _Conv1x1Fn(torch.autograd.Function):
                 dx = torch.zeros_like(x)
             dx[:, :, ::2, ::2].add_(sub.to(dx.dtype))
         if ctx.needs_input_grad[1]:
-            if wgrad == "k9":
-                dw = _k9_wgrad(dy, x, w)
-            else:
-                dw = _conv1x1_wgrad_lib(dy, x, w)
+            dw = _routed_conv1x1_wgrad(wgrad, dy, x, w)
         return dx, dw, None, None
 
 
@@ -833,14 +865,9 @@ def conv1x1(x: torch.Tensor, w: torch.Tensor, *, stats: bool = False, fork: bool
     added inside this convolution's data-grad kernel; ``fork=2``: return the compact stride-2
     subsample of ``x`` instead (see :class:`_Conv1x1Fn`)."""
     _need_native("conv1x1")
-    outs = _Conv1x1Fn.apply(x, w, stats, fork)
-    y, part = outs[0], outs[1]
-    ret = [y]
-    if stats:
-        ret.append(part if part.numel() else None)
-    if fork:
-        ret.append(outs[2])
-    return ret[0] if len(ret) == 1 else tuple(ret)
+    y, part, *side = _Conv1x1Fn.apply(x, w, stats, fork)
+    ret = (y, part if part.numel() else None, *side) if stats else (y, *side)
+    return ret[0] if len(ret) == 1 else ret
 
 
 class _BNReluConv1x1EpiFn(torch.autograd.Function):
@@ -851,15 +878,9 @@ class _BNReluConv1x1EpiFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, w, bn_w, bn_b, bn, stats_in, want_stats):
-        a, mean, invstd, scale, shift, _ = torch.ops.madnn.bn_fwd(y, None, bn_w, bn_b, bn.running_mean,
-                                                                  bn.running_var, bn.num_batches_tracked, True,
-                                                                  float(bn.momentum), float(bn.eps), True, stats_in)
+        a, mean, invstd, scale, shift, _ = _bn_fwd_train(y, None, bn_w, bn_b, bn, True, stats_in)
         fwd, _, wgrad = conv1x1_route(a.size(1), w.size(0))
-        if fwd == "k9":
-            out, part = torch.ops.madnn.conv1x1_fwd(a, w, bool(want_stats))
-        else:
-            out = torch.nn.functional.conv2d(a, w) if a.dim() == 4 else torch.mm(a, w.reshape(w.size(0), -1).t())
-            part = a.new_empty((0, 2, w.size(0)), dtype=torch.float32)
+        out, part = _routed_conv1x1_fwd(fwd, a, w, want_stats)
         ctx.save_for_backward(y, a, w, bn_w, mean, invstd, scale, shift)
         ctx.wgrad = wgrad
         ctx.mark_non_differentiable(part)
@@ -870,26 +891,23 @@ class _BNReluConv1x1EpiFn(torch.autograd.Function):
         y, a, w, bn_w, mean, invstd, scale, shift = ctx.saved_tensors
         dout = _nhwc(dout.to(y.dtype))
         da, part = torch.ops.madnn.conv1x1_dgrad_bnb(dout, w, y, scale, shift)
-        if ctx.wgrad == "k9":
-            dw = _k9_wgrad(dout, a, w)
-        else:
-            dw = _conv1x1_wgrad_lib(dout, a, w)
+        dw = _routed_conv1x1_wgrad(ctx.wgrad, dout, a, w)
         dy, dbw, dbb = torch.ops.madnn.bn_bwd_ext(da, y, bn_w, mean, invstd, scale, shift, part, True)
         need_bn = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         return dy, dw, dbw if need_bn else None, dbb if need_bn else None, None, None, None
 
 
 def bn_relu_conv1x1(y: torch.Tensor, bn, w: torch.Tensor, *, stats_in: Optional[torch.Tensor] = None,
-                    stats: bool = False):
+                    stats: bool = False, checked: bool = False):
     """``conv1x1(relu(bn(y)), w)`` (ResNet's bn2 -> conv3): when the data grad runs on K9, bn's
     backward reduction is taken in that kernel's epilogue.  ``stats_in``: ``y``'s partial
     statistics from its producer; ``stats``: also return the output's partial statistics (None if
-    not computed).  (A BatchNorm-apply prologue inside K9's operand load lost its A/B --
+    not computed); ``checked``: the caller asked :func:`bn_relu_conv1x1_epi_supported` already (yes).
+    (A BatchNorm-apply prologue inside K9's operand load lost its A/B --
     profiles/r2_ab_bn_prologue.json -- and was removed in round 6.)"""
-    if bn_relu_conv1x1_epi_supported(y, bn, w):
+    if checked or bn_relu_conv1x1_epi_supported(y, bn, w):
         _need_native("bn_relu_conv1x1")
-        out, part = _BNReluConv1x1EpiFn.apply(y, w, bn.weight, bn.bias, bn, stats_in, stats)
-        return (out, part if part.numel() else None) if stats else out
+        return _with_stats(*_BNReluConv1x1EpiFn.apply(y, w, bn.weight, bn.bias, bn, stats_in, stats), stats)
     a = bn(y, relu=True, stats=stats_in) if _is_fused_bn(bn) else torch.relu(bn(y))
     if conv1x1_supported(a, w):
         return conv1x1(a, w, stats=stats)
@@ -901,10 +919,25 @@ def bn_relu_conv1x1(y: torch.Tensor, bn, w: torch.Tensor, *, stats_in: Optional[
 def bn_relu_conv1x1_epi_supported(y: torch.Tensor, bn, w: torch.Tensor) -> bool:
     """The data-grad-epilogue variant of :func:`bn_relu_conv1x1`: training BN (running stats, fp32
     affine) in front of a 1x1 convolution whose data grad routes to K9."""
-    return (_BN_DGRAD_EPI and isinstance(y, torch.Tensor) and bn.training and bn.track_running_stats
-            and bn.affine and bn.momentum is not None and bn.weight.dtype == torch.float32
+    return (_BN_DGRAD_EPI and isinstance(y, torch.Tensor) and _bn_trainable(bn)
             and conv1x1_supported(y, w) and bn_supported(y, bn.weight)
             and conv1x1_route(y.size(1), w.size(0))[1] == "k9")
+
+
+def _k9f_head(y2, w3, bn2_w, bn2_b, bn2, stats_in):
+    """Both K9F nodes' forward up to conv3 -> (a2, y3, y3's statistics, bn2's (mean, invstd, scale, shift))."""
+    a2, mean2, invstd2, scale2, shift2, _ = _bn_fwd_train(y2, None, bn2_w, bn2_b, bn2, True, stats_in)
+    y3, part = torch.ops.madnn.conv1x1_fwd(a2, w3, True)
+    return a2, y3, part, (mean2, invstd2, scale2, shift2)
+
+
+def _k9f_tail(ctx, da2, part, y2, bn2_w, bn2_stats, dw3, w3, dbw3, dbb3):
+    """Both K9F nodes' backward after the fused kernel: bn2's finalize + apply, then the gradients of the six
+    inputs the nodes share (y2, w3, bn2's and bn3's affine pairs, a pair only if one of it is needed)."""
+    dy2, dbw2, dbb2 = torch.ops.madnn.bn_bwd_ext(da2, y2, bn2_w, *bn2_stats, part, True)
+    need2, need3 = (ctx.needs_input_grad[i] or ctx.needs_input_grad[i + 1] for i in (2, 4))
+    return (dy2, dw3.to(w3.dtype).view(w3.shape), dbw2 if need2 else None, dbb2 if need2 else None,
+            dbw3 if need3 else None, dbb3 if need3 else None)
 
 
 class _BN2Conv3BN3Fn(torch.autograd.Function):
@@ -917,54 +950,45 @@ class _BN2Conv3BN3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y2, w3, bn2_w, bn2_b, bn3_w, bn3_b, idt, bn2, bn3, stats_in):
-        a2, mean2, invstd2, scale2, shift2, _ = torch.ops.madnn.bn_fwd(
-            y2, None, bn2_w, bn2_b, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked, True,
-            float(bn2.momentum), float(bn2.eps), True, stats_in)
-        y3, part = torch.ops.madnn.conv1x1_fwd(a2, w3, True)
-        out, mean3, invstd3, scale3, shift3, mask = torch.ops.madnn.bn_fwd(
-            y3, idt, bn3_w, bn3_b, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked, True,
-            float(bn3.momentum), float(bn3.eps), True, part)
-        ctx.save_for_backward(y2, a2, w3, y3, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3, invstd3,
-                              scale3, shift3)
+        a2, y3, part, bn2_stats = _k9f_head(y2, w3, bn2_w, bn2_b, bn2, stats_in)
+        out, mean3, invstd3, scale3, shift3, mask = _bn_fwd_train(y3, idt, bn3_w, bn3_b, bn3, True, part)
+        ctx.save_for_backward(y2, a2, w3, y3, mask, bn2_w, *bn2_stats, bn3_w, mean3, invstd3, scale3, shift3)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        (y2, a2, w3, y3, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3, invstd3, scale3,
-         shift3) = ctx.saved_tensors
-        if dout.dtype != y3.dtype or dout.stride() != y3.stride():
-            dout = torch.empty_like(y3).copy_(dout)
+        y2, a2, w3, y3, mask, bn2_w, *bn2_stats, bn3_w, mean3, invstd3, scale3, shift3 = ctx.saved_tensors
+        dout = _like(dout, y3)
         coef, dbw3, dbb3 = torch.ops.madnn.bn_bwd_coef(dout, y3, mask, bn3_w, mean3, invstd3, scale3, shift3)
-        da2, part, dw3 = torch.ops.madnn.bn3_conv3_bwd(dout, y3, mask, coef, w3, a2, y2, scale2, shift2,
+        da2, part, dw3 = torch.ops.madnn.bn3_conv3_bwd(dout, y3, mask, coef, w3, a2, y2, *bn2_stats[2:],
                                                        w3.dtype == torch.bfloat16)
-        dy2, dbw2, dbb2 = torch.ops.madnn.bn_bwd_ext(da2, y2, bn2_w, mean2, invstd2, scale2, shift2, part, True)
+        grads = _k9f_tail(ctx, da2, part, y2, bn2_w, bn2_stats, dw3, w3, dbw3, dbb3)
         dres = dout.view_as(dout)
         _attach(dres, "_madnn_resmask", mask)
-        need2 = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
-        need3 = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
-        return (dy2, dw3.to(w3.dtype).view(w3.shape), dbw2 if need2 else None, dbb2 if need2 else None,
-                dbw3 if need3 else None, dbb3 if need3 else None, dres, None, None, None)
+        return (*grads, dres, None, None, None)
 
 
 _BN3_CONV3_FUSED = os.environ.get("MADNN_BN3_CONV3_FUSED", "1") != "0"  # A/B switch (K9F)
+
+
+def _k9f_supported(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, other: torch.Tensor) -> bool:
+    """What both K9F predicates ask: channels the fused kernel takes, bn2 and bn3 trainable, conv3 on K9 both ways,
+    ``y2`` needing its gradient, ``other`` (the identity / the downsample input) of its dtype, batch and pixels."""
+    return (_BN3_CONV3_FUSED and isinstance(y2, torch.Tensor) and isinstance(other, torch.Tensor)
+            and bn_relu_conv1x1_epi_supported(y2, bn2, w3) and native_available()
+            and bool(torch.ops.madnn.bn3_conv3_bwd_supported(y2.size(1), w3.size(0)))
+            and conv1x1_route(y2.size(1), w3.size(0))[0] == "k9" and _bn_trainable(bn3)
+            and bn3.weight.numel() == w3.size(0) and y2.requires_grad and torch.is_grad_enabled()
+            and other.dtype == y2.dtype and other.dim() == y2.dim() and other.size(0) == y2.size(0)
+            and other.shape[2:] == y2.shape[2:])
 
 
 def bn2_conv3_bn3_supported(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, idt: torch.Tensor) -> bool:
     """Inputs :func:`bn2_conv3_bn3_add_relu` runs with the fused backward kernel: the layer-1 identity
     bottleneck shape (64 -> 256 channels), both BatchNorms training with fp32 affine parameters, conv3's
     forward and data grad on K9, and an identity whose ReLU mask is deferred to its consumer."""
-    def ok(m):
-        return (m.training and m.track_running_stats and m.affine and m.momentum is not None
-                and m.weight.dtype == torch.float32)
-    if not (_BN3_CONV3_FUSED and DEFER_RES_MASK and isinstance(y2, torch.Tensor) and isinstance(idt, torch.Tensor)):
-        return False
-    c, c4 = y2.size(1), w3.size(0)
-    return (bn_relu_conv1x1_epi_supported(y2, bn2, w3) and native_available()
-            and bool(torch.ops.madnn.bn3_conv3_bwd_supported(c, c4)) and conv1x1_route(c, c4)[0] == "k9" and ok(bn2) and ok(bn3)
-            and bn3.weight.numel() == c4 and y2.requires_grad and torch.is_grad_enabled()
-            and getattr(idt, "_madnn_defer_mask", False) and idt.dtype == y2.dtype and idt.dim() == y2.dim()
-            and idt.size(1) == c4 and idt.shape[2:] == y2.shape[2:] and idt.size(0) == y2.size(0)
-            and bn_supported(idt, bn3.weight))
+    return (DEFER_RES_MASK and _k9f_supported(y2, bn2, w3, bn3, idt) and _res_mask_deferred(idt)
+            and idt.size(1) == w3.size(0) and bn_supported(idt, bn3.weight))
 
 
 def bn2_conv3_bn3_add_relu(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, idt: torch.Tensor,
@@ -985,37 +1009,31 @@ class _BN2Conv3BN3DualFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y2, w3, bn2_w, bn2_b, bn3_w, bn3_b, xf, w_ds, bnd_w, bnd_b, bn2, bn3, bn_ds, stats_in):
-        a2, mean2, invstd2, scale2, shift2, _ = torch.ops.madnn.bn_fwd(
-            y2, None, bn2_w, bn2_b, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked, True,
-            float(bn2.momentum), float(bn2.eps), True, stats_in)
-        y3, part = torch.ops.madnn.conv1x1_fwd(a2, w3, True)
+        a2, y3, part, bn2_stats = _k9f_head(y2, w3, bn2_w, bn2_b, bn2, stats_in)
         yd, part_d = torch.ops.madnn.conv1x1_fwd(xf, w_ds, True)
         out, mask, mean3, invstd3, _, _, mean_d, invstd_d, _, _ = torch.ops.madnn.bn_fwd_dual(
             y3, yd, bn3_w, bn3_b, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked, float(bn3.momentum),
             float(bn3.eps), part, bnd_w, bnd_b, bn_ds.running_mean, bn_ds.running_var, bn_ds.num_batches_tracked,
             float(bn_ds.momentum), float(bn_ds.eps), part_d)
-        ctx.save_for_backward(y2, a2, w3, y3, xf, w_ds, yd, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3,
-                              invstd3, bnd_w, mean_d, invstd_d)
+        ctx.save_for_backward(y2, a2, w3, y3, xf, w_ds, yd, mask, bn2_w, *bn2_stats, bn3_w, mean3, invstd3, bnd_w,
+                              mean_d, invstd_d)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        (y2, a2, w3, y3, xf, w_ds, yd, mask, bn2_w, mean2, invstd2, scale2, shift2, bn3_w, mean3, invstd3, bnd_w,
-         mean_d, invstd_d) = ctx.saved_tensors
-        if dout.dtype != y3.dtype or dout.stride() != y3.stride():
-            dout = torch.empty_like(y3).copy_(dout)
+        (y2, a2, w3, y3, xf, w_ds, yd, mask, bn2_w, *bn2_stats, bn3_w, mean3, invstd3, bnd_w, mean_d,
+         invstd_d) = ctx.saved_tensors
+        dout = _like(dout, y3)
         coef, dbw3, dbb3, dbwd, dbbd = torch.ops.madnn.bn_bwd_dual_coef(dout, y3, yd, mask, bn3_w, mean3, invstd3,
                                                                         bnd_w, mean_d, invstd_d)
-        da2, part, dw3 = torch.ops.madnn.bn3_conv3_bwd(dout, y3, mask, coef[:3], w3, a2, y2, scale2, shift2,
+        da2, part, dw3 = torch.ops.madnn.bn3_conv3_bwd(dout, y3, mask, coef[:3], w3, a2, y2, *bn2_stats[2:],
                                                        w3.dtype == torch.bfloat16)
         dxf, _, dwd = torch.ops.madnn.bn3_conv3_bwd(dout, yd, mask, coef[3:], w_ds, xf, None, None, None,
                                                     w_ds.dtype == torch.bfloat16)
-        dy2, dbw2, dbb2 = torch.ops.madnn.bn_bwd_ext(da2, y2, bn2_w, mean2, invstd2, scale2, shift2, part, True)
-        need = ctx.needs_input_grad
-        need2, need3, needd = need[2] or need[3], need[4] or need[5], need[8] or need[9]
-        return (dy2, dw3.to(w3.dtype).view(w3.shape), dbw2 if need2 else None, dbb2 if need2 else None,
-                dbw3 if need3 else None, dbb3 if need3 else None, dxf, dwd.to(w_ds.dtype).view(w_ds.shape),
-                dbwd if needd else None, dbbd if needd else None, None, None, None, None)
+        grads = _k9f_tail(ctx, da2, part, y2, bn2_w, bn2_stats, dw3, w3, dbw3, dbb3)
+        needd = ctx.needs_input_grad[8] or ctx.needs_input_grad[9]
+        return (*grads, dxf, dwd.to(w_ds.dtype).view(w_ds.shape), dbwd if needd else None,
+                dbbd if needd else None, None, None, None, None)
 
 
 # A/B switch: K9F also on the layer-1 downsample block (both convolutions); honoured while _BN3_CONV3_FUSED is on
@@ -1029,19 +1047,9 @@ def bn2_conv3_bn3_add_bn_relu_supported(y2: torch.Tensor, bn2, w3: torch.Tensor,
     channels, ``xf`` of ``y2``'s pixels), all three BatchNorms training with fp32 affine parameters, and both
     convolutions' forward and data grad on K9.  (That ``w_ds`` belongs to a stride-1 1x1 convolution is the
     caller's to check.)"""
-    def ok(m):
-        return (m.training and m.track_running_stats and m.affine and m.momentum is not None
-                and m.weight.dtype == torch.float32)
-    if not (_BN3_CONV3_FUSED and _BN3_CONV3_DUAL and isinstance(y2, torch.Tensor) and isinstance(xf, torch.Tensor)):
-        return False
-    c, c4 = y2.size(1), w3.size(0)
-    return (bn_relu_conv1x1_epi_supported(y2, bn2, w3) and native_available()
-            and bool(torch.ops.madnn.bn3_conv3_bwd_supported(c, c4)) and conv1x1_route(c, c4)[:2] == ("k9", "k9")
-            and conv1x1_supported(xf, w_ds) and xf.size(1) == c and w_ds.size(0) == c4
-            and ok(bn2) and ok(bn3) and ok(bn_ds) and bn3.weight.numel() == c4 and bn_ds.weight.numel() == c4
-            and y2.requires_grad and torch.is_grad_enabled()
-            and xf.dtype == y2.dtype and xf.dim() == y2.dim() and xf.size(0) == y2.size(0)
-            and xf.shape[2:] == y2.shape[2:])
+    return (_BN3_CONV3_DUAL and _k9f_supported(y2, bn2, w3, bn3, xf) and conv1x1_supported(xf, w_ds)
+            and xf.size(1) == y2.size(1) and w_ds.size(0) == w3.size(0) and _bn_trainable(bn_ds)
+            and bn_ds.weight.numel() == w3.size(0))
 
 
 def bn2_conv3_bn3_add_bn_relu(y2: torch.Tensor, bn2, w3: torch.Tensor, bn3, xf: torch.Tensor, w_ds: torch.Tensor,
@@ -1077,13 +1085,11 @@ class _BNReluMaxPoolFn(torch.autograd.Function):
 
 def bn_relu_maxpool_supported(y: torch.Tensor, bn, pool) -> bool:
     """The stem shape the fused BN + ReLU + 3x3/s2 max-pool takes (training BN, bf16 NHWC)."""
-    def pair(v):
-        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
     return (_POOL_BN and isinstance(y, torch.Tensor) and y.device.type == "cuda" and y.dtype == torch.bfloat16 and y.dim() == 4
-            and y.is_contiguous(memory_format=torch.channels_last) and bn.training and bn.track_running_stats
-            and bn.affine and bn.momentum is not None and bn.weight.dtype == torch.float32
-            and pair(pool.kernel_size) == (3, 3) and pair(pool.stride) == (2, 2) and pair(pool.padding) in ((1, 1), (0, 0))
-            and pair(pool.dilation) == (1, 1) and not pool.ceil_mode and not pool.return_indices
+            and y.is_contiguous(memory_format=torch.channels_last) and _bn_trainable(bn)
+            and _pair(pool.kernel_size) == (3, 3) and _pair(pool.stride) == (2, 2)
+            and _pair(pool.padding) in ((1, 1), (0, 0)) and _pair(pool.dilation) == (1, 1)
+            and not pool.ceil_mode and not pool.return_indices
             and y.size(1) % 8 == 0 and 256 % (y.size(1) // 8) == 0 and y.numel() < 2 ** 31)
 
 
@@ -1117,20 +1123,26 @@ def _k13_halo_ok(W: int) -> bool:
     return max(cap * rb + rb + 2 * 64 * rb, 32 * 1024) <= 80 * 1024
 
 
-def conv3x3_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
-    """Inputs K13 takes: NHWC bf16 HIP activations, bf16 [Co, Ci, 3, 3] weight, Ci and Co multiples
-    of 64, image width whose input halo fits the kernel's LDS budget (W <= 56 or so)."""
+def _k13_operands_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """K13's operands at either stride: NHWC bf16 HIP activations, bf16 [Co, Ci, 3, 3] weight, channels % 64."""
     if not _K13 or x.device.type != "cuda" or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
         return False
     if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last) or x.numel() == 0:
         return False
     if w.dim() != 4 or tuple(w.shape[1:]) != (x.size(1), 3, 3):
         return False
-    return x.size(1) % 64 == 0 and w.size(0) % 64 == 0 and _k13_halo_ok(x.size(3))
+    return x.size(1) % 64 == 0 and w.size(0) % 64 == 0
 
 
-def _cl(t: torch.Tensor) -> torch.Tensor:
-    return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+def conv3x3_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """Inputs K13 takes: NHWC bf16 HIP activations, bf16 [Co, Ci, 3, 3] weight, Ci and Co multiples
+    of 64, image width whose input halo fits the kernel's LDS budget (W <= 56 or so)."""
+    return _k13_operands_ok(x, w) and _k13_halo_ok(x.size(3))
+
+
+def _flip3x3(w: torch.Tensor) -> torch.Tensor:
+    """The weight K13 runs a data grad with: W'[ci][kh][kw][co] = W[co][2-kh][2-kw][ci], channels_last."""
+    return w.flip(2, 3).transpose(0, 1).contiguous(memory_format=torch.channels_last)
 
 
 def _conv3x3_wgrad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -1149,9 +1161,7 @@ def _conv3x3_wgrad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.
         dw = k13()
     else:
         dw = tuned_wgrad(("conv3x3",) + tuple(x.shape) + (w.size(0),), lib, k13)
-    if dw.stride() != w.stride() or dw.dtype != w.dtype:
-        dw = torch.empty_like(w).copy_(dw)
-    return dw
+    return _like(dw, w)
 
 
 class _Conv3x3Fn(torch.autograd.Function):
@@ -1162,7 +1172,7 @@ class _Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, stats):
-        y, part = torch.ops.madnn.conv3x3_fwd(x, _cl(w), bool(stats))
+        y, part = torch.ops.madnn.conv3x3_fwd(x, _nhwc(w), bool(stats))
         ctx.save_for_backward(x, w)
         ctx.mark_non_differentiable(part)
         return y, part
@@ -1173,8 +1183,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         dy = _nhwc(dy.to(x.dtype))
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            wt = w.flip(2, 3).transpose(0, 1).contiguous(memory_format=torch.channels_last)
-            dx = torch.ops.madnn.conv3x3_fwd(dy, wt, False)[0]
+            dx = torch.ops.madnn.conv3x3_fwd(dy, _flip3x3(w), False)[0]
         if ctx.needs_input_grad[1]:
             dw = _conv3x3_wgrad(dy, x, w)
         return dx, dw, None
@@ -1188,10 +1197,8 @@ class _BNReluConv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, w, bn_w, bn_b, bn, stats_in, want_stats):
-        a, mean, invstd, scale, shift, _ = torch.ops.madnn.bn_fwd(y, None, bn_w, bn_b, bn.running_mean,
-                                                                  bn.running_var, bn.num_batches_tracked, True,
-                                                                  float(bn.momentum), float(bn.eps), True, stats_in)
-        out, part = torch.ops.madnn.conv3x3_fwd(a, _cl(w), bool(want_stats))
+        a, mean, invstd, scale, shift, _ = _bn_fwd_train(y, None, bn_w, bn_b, bn, True, stats_in)
+        out, part = torch.ops.madnn.conv3x3_fwd(a, _nhwc(w), bool(want_stats))
         ctx.save_for_backward(y, a, w, bn_w, mean, invstd, scale, shift)
         ctx.mark_non_differentiable(part)
         return out, part
@@ -1200,8 +1207,7 @@ class _BNReluConv3x3Fn(torch.autograd.Function):
     def backward(ctx, dout, _dpart):
         y, a, w, bn_w, mean, invstd, scale, shift = ctx.saved_tensors
         dout = _nhwc(dout.to(y.dtype))
-        wt = w.flip(2, 3).transpose(0, 1).contiguous(memory_format=torch.channels_last)
-        da, part = torch.ops.madnn.conv3x3_fwd_bnb(dout, wt, y, scale, shift)
+        da, part = torch.ops.madnn.conv3x3_fwd_bnb(dout, _flip3x3(w), y, scale, shift)
         dw = _conv3x3_wgrad(dout, a, w)
         dy, dbw, dbb = torch.ops.madnn.bn_bwd_ext(da, y, bn_w, mean, invstd, scale, shift, part, True)
         need_bn = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
@@ -1211,20 +1217,18 @@ class _BNReluConv3x3Fn(torch.autograd.Function):
 def bn_relu_conv3x3_supported(y: torch.Tensor, bn, w: torch.Tensor) -> bool:
     """Whether :func:`bn_relu_conv3x3` runs fused: training-mode BN with running statistics and an
     fp32 affine in front of a K13-shaped convolution whose data grad runs on K13."""
-    return (_BN_DGRAD_EPI and isinstance(y, torch.Tensor) and bn.training
-            and bn.track_running_stats and bn.affine and bn.momentum is not None
-            and bn.weight.dtype == torch.float32 and conv3x3_supported(y, w) and y.size(1) == w.size(1)
-            and bn_supported(y, bn.weight))
+    return (_BN_DGRAD_EPI and isinstance(y, torch.Tensor) and _bn_trainable(bn) and conv3x3_supported(y, w)
+            and y.size(1) == w.size(1) and bn_supported(y, bn.weight))
 
 
 def bn_relu_conv3x3(y: torch.Tensor, bn, w: torch.Tensor, *, stats_in: Optional[torch.Tensor] = None,
-                    stats: bool = False):
+                    stats: bool = False, checked: bool = False):
     """``conv3x3(relu(bn(y)), w)`` with bn's backward reduction taken in K13's data-grad epilogue
-    (:class:`_BNReluConv3x3Fn`); composition of the two modules' paths otherwise."""
-    if bn_relu_conv3x3_supported(y, bn, w):
+    (:class:`_BNReluConv3x3Fn`); composition of the two modules' paths otherwise.  ``checked``: the caller
+    asked :func:`bn_relu_conv3x3_supported` already (yes)."""
+    if checked or bn_relu_conv3x3_supported(y, bn, w):
         _need_native("bn_relu_conv3x3")
-        out, part = _BNReluConv3x3Fn.apply(y, w, bn.weight, bn.bias, bn, stats_in, stats)
-        return (out, part if part.numel() else None) if stats else out
+        return _with_stats(*_BNReluConv3x3Fn.apply(y, w, bn.weight, bn.bias, bn, stats_in, stats), stats)
     a = bn(y, relu=True, stats=stats_in) if _is_fused_bn(bn) else torch.relu(bn(y))
     if conv3x3_supported(a, w):
         return conv3x3(a, w, stats=stats)
@@ -1255,15 +1259,8 @@ _K13_S2_MAX_W = int(os.environ.get("MADNN_CONV3X3_S2_MAX_W", "16"))
 
 def conv3x3_s2_supported(x: torch.Tensor, w: torch.Tensor) -> bool:
     """The stride-2 / pad-1 3x3 inputs K13 takes (even H and W up to ``MADNN_CONV3X3_S2_MAX_W``)."""
-    if not _K13 or x.device.type != "cuda" or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
-        return False
-    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last) or x.numel() == 0:
-        return False
-    if w.dim() != 4 or tuple(w.shape[1:]) != (x.size(1), 3, 3):
-        return False
-    H, W = x.size(2), x.size(3)
-    return (x.size(1) % 64 == 0 and w.size(0) % 64 == 0 and H % 2 == 0 and W % 2 == 0 and 2 <= W <= _K13_S2_MAX_W
-            and H <= 4 * _K13_S2_MAX_W)
+    return (_k13_operands_ok(x, w) and x.size(2) % 2 == 0 and x.size(3) % 2 == 0
+            and 2 <= x.size(3) <= _K13_S2_MAX_W and x.size(2) <= 4 * _K13_S2_MAX_W)
 
 
 class _Conv3x3S2Fn(torch.autograd.Function):
@@ -1273,7 +1270,7 @@ class _Conv3x3S2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, stats):
-        y, part = torch.ops.madnn.conv3x3_fwd_s2(x, _cl(w), bool(stats))
+        y, part = torch.ops.madnn.conv3x3_fwd_s2(x, _nhwc(w), bool(stats))
         ctx.save_for_backward(x, w)
         ctx.mark_non_differentiable(part)
         return y, part
@@ -1340,9 +1337,7 @@ class _StemFn(torch.autograd.Function):
             dx = torch.ops.aten.convolution_backward(dy, x, w, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1,
                                                      (True, False, False))[0]
         if ctx.needs_input_grad[1]:
-            dw = torch.ops.madnn.stem_wgrad(dy, x).to(w.dtype)
-            if not dw.is_contiguous(memory_format=torch.contiguous_format) or w.stride() != dw.stride():
-                dw = torch.empty_like(w).copy_(dw)
+            dw = _like(torch.ops.madnn.stem_wgrad(dy, x).to(w.dtype), w)
         return dx, dw, None
 
 

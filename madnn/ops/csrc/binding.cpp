@@ -375,6 +375,43 @@ const float* optf(const c10::optional<at::Tensor>& t) {
 
 float* optf_mut(const c10::optional<at::Tensor>& t) { return const_cast<float*>(optf(t)); }
 
+// The [rows, 2, C] fp32 partial statistics a producer's epilogue left, or null when absent or empty.
+const float* partial_ptr(const c10::optional<at::Tensor>& p, int64_t C, const char* op) {
+  if (!p.has_value() || !p->defined() || p->numel() == 0) return nullptr;
+  TORCH_CHECK(p->scalar_type() == at::kFloat && p->is_contiguous() && p->dim() == 3 && p->size(1) == 2 &&
+                  p->size(2) == C,
+              op, ": partial statistics must be fp32 [rows, 2, C]");
+  return p->data_ptr<float>();
+}
+
+int64_t* nbt_ptr(const c10::optional<at::Tensor>& t, const char* op) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->scalar_type() == at::kLong && t->is_cuda(), op, ": num_batches_tracked must be int64 on the device");
+  return t->data_ptr<int64_t>();
+}
+
+// dy in x's strides and dtype (a copy only if it is not already)
+at::Tensor dy_like(const at::Tensor& dy, const at::Tensor& x) {
+  if (dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type()) return dy;
+  return at::empty_like(x).copy_(dy);
+}
+
+// A ReLU bit mask over `numel` elements, 8 per byte in memory order.
+const uint8_t* mask_ptr(const c10::optional<at::Tensor>& mask, int64_t numel, const char* op) {
+  TORCH_CHECK(mask.has_value() && mask->defined() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
+                  mask->numel() == numel / 8,
+              op, ": ReLU bit mask required");
+  return mask->data_ptr<uint8_t>();
+}
+
+// A per-channel fp32 vector (a BatchNorm's scale or shift) of C elements, on the device.
+const float* vec_ptr(const at::Tensor& v, int64_t C, const char* op, const char* what) {
+  check_dev(v, what);
+  TORCH_CHECK(v.numel() == C && v.scalar_type() == at::kFloat && v.is_contiguous(), op, ": ", what,
+              " must be fp32 [", C, "]");
+  return v.data_ptr<float>();
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_fwd(
     const at::Tensor& x, const c10::optional<at::Tensor>& res, const c10::optional<at::Tensor>& w,
     const c10::optional<at::Tensor>& b, const c10::optional<at::Tensor>& run_mean,
@@ -392,30 +429,20 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
   at::Tensor save_mean = at::empty({C}, fo), save_invstd = at::empty({C}, fo);
   at::Tensor scale = at::empty({C}, fo), shift = at::empty({C}, fo);
   // statistics produced upstream (K9 conv epilogue): [rows, 2, C] partial sums
-  const bool ext = training && partial.has_value() && partial->defined() && partial->numel() > 0;
-  if (ext) {
-    TORCH_CHECK(partial->scalar_type() == at::kFloat && partial->is_contiguous() && partial->dim() == 3 &&
-                    partial->size(1) == 2 && partial->size(2) == C,
-                "bn: partial statistics must be fp32 [rows, 2, C]");
-  }
+  const float* ext = training ? partial_ptr(partial, C, "bn_fwd") : nullptr;
   at::Tensor ws = at::empty({training && !ext ? (int64_t)madnn_bn_partial_rows(M, (int)C) * 2 * C
                                               : (int64_t)madnn_bn_prereduce_floats((int)C)},
                             fo);
   // training with a fused residual + ReLU: 1-bit ReLU mask for the backward passes
   const bool need_mask = training && relu && res.has_value();
   at::Tensor mask = at::empty({need_mask ? x.numel() / 8 : 0}, x.options().dtype(at::kByte));
-  int64_t* nb = nullptr;
-  if (nbt.has_value() && nbt->defined()) {
-    TORCH_CHECK(nbt->scalar_type() == at::kLong && nbt->is_cuda(), "num_batches_tracked must be an int64 device tensor");
-    nb = nbt->data_ptr<int64_t>();
-  }
   check(madnn_bn_fwd(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr, y.data_ptr(),
                      need_mask ? mask.data_ptr<uint8_t>() : nullptr, M, (int)C, dt_code(x),
                      relu ? 1 : 0, training ? 1 : 0, (float)eps, (float)momentum, optf(w), optf(b),
                      training ? optf_mut(run_mean) : const_cast<float*>(optf(run_mean)), optf_mut(run_var),
-                     training ? nb : nullptr, save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
+                     training ? nbt_ptr(nbt, "bn_fwd") : nullptr, save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
                      scale.data_ptr<float>(), shift.data_ptr<float>(), ws.data_ptr<float>(),
-                     ext ? partial->data_ptr<float>() : nullptr, ext ? (int)partial->size(0) : 0, cur_stream(x)),
+                     ext, ext ? (int)partial->size(0) : 0, cur_stream(x)),
         "bn_fwd");
   return {y, save_mean, save_invstd, scale, shift, mask};
 }
@@ -428,21 +455,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_bwd(
   const int64_t C = x.size(1);
   const int64_t M = bn_rows(x, C);
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  at::Tensor dyc = dy;
-  if (dy.strides() != x.strides() || dy.scalar_type() != x.scalar_type()) {
-    dyc = at::empty_like(x);
-    dyc.copy_(dy);
-  }
+  at::Tensor dyc = dy_like(dy, x);
   at::Tensor dx = at::empty_like(x);
   // !write_dres (ReLU + residual only): the residual's gradient (dy masked by the ReLU) is left to
   // the consumer, which reads dy and the bit mask itself (conv1x1_dgrad resmask)
   TORCH_CHECK(write_dres || (relu && has_res), "bn_bwd: write_dres=False needs ReLU + residual");
   at::Tensor dres = has_res && write_dres ? at::empty_like(x) : at::Tensor();
-  const uint8_t* mk = nullptr;
-  if (relu && has_res) {
-    TORCH_CHECK(mask.has_value() && mask->numel() == x.numel() / 8, "bn_bwd: ReLU bit mask required");
-    mk = mask->data_ptr<uint8_t>();
-  }
+  const uint8_t* mk = relu && has_res ? mask_ptr(mask, x.numel(), "bn_bwd") : nullptr;
   auto fo = x.options().dtype(at::kFloat);
   at::Tensor dw = at::empty({C}, fo), db = at::empty({C}, fo);
   at::Tensor coef = at::empty({3 * C}, fo);
@@ -478,18 +497,6 @@ std::vector<at::Tensor> bn_fwd_dual(const at::Tensor& x, const at::Tensor& r, co
   TORCH_CHECK(r.sizes() == x.sizes() && r.strides() == x.strides(), "bn_fwd_dual: residual layout");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto fo = x.options().dtype(at::kFloat);
-  auto ext = [&](const c10::optional<at::Tensor>& p) -> const float* {
-    if (!p.has_value() || !p->defined() || p->numel() == 0) return nullptr;
-    TORCH_CHECK(p->scalar_type() == at::kFloat && p->is_contiguous() && p->dim() == 3 && p->size(1) == 2 &&
-                    p->size(2) == C,
-                "bn: partial statistics must be fp32 [rows, 2, C]");
-    return p->data_ptr<float>();
-  };
-  auto nbp = [](const c10::optional<at::Tensor>& t) -> int64_t* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    TORCH_CHECK(t->scalar_type() == at::kLong && t->is_cuda(), "num_batches_tracked must be an int64 device tensor");
-    return t->data_ptr<int64_t>();
-  };
   std::vector<at::Tensor> out;
   out.push_back(at::empty_like(x));
   out.push_back(at::empty({x.numel() / 8}, x.options().dtype(at::kByte)));
@@ -497,14 +504,16 @@ std::vector<at::Tensor> bn_fwd_dual(const at::Tensor& x, const at::Tensor& r, co
   at::Tensor ws = at::empty({std::max<int64_t>((int64_t)madnn_bn_partial_rows(M, (int)C) * 2 * C,
                                                (int64_t)madnn_bn_prereduce_floats((int)C))},
                             fo);
-  const float* pe = ext(partial);
-  const float* pr = ext(partial_r);
+  const float* pe = partial_ptr(partial, C, "bn_fwd_dual");
+  const float* pr = partial_ptr(partial_r, C, "bn_fwd_dual");
+  int64_t* nb = nbt_ptr(nbt, "bn_fwd_dual");
+  int64_t* nb_r = nbt_ptr(nbt_r, "bn_fwd_dual");
   check(madnn_bn_fwd_dual(x.data_ptr(), r.data_ptr(), out[0].data_ptr(), out[1].data_ptr<uint8_t>(), M, (int)C,
                           (float)eps, (float)momentum, optf(w), optf(b), optf_mut(run_mean), optf_mut(run_var),
-                          nbp(nbt), out[2].data_ptr<float>(), out[3].data_ptr<float>(), out[4].data_ptr<float>(),
+                          nb, out[2].data_ptr<float>(), out[3].data_ptr<float>(), out[4].data_ptr<float>(),
                           out[5].data_ptr<float>(), pe, pe ? (int)partial->size(0) : 0, (float)eps_r,
                           (float)momentum_r, optf(w_r), optf(b_r), optf_mut(run_mean_r), optf_mut(run_var_r),
-                          nbp(nbt_r), out[6].data_ptr<float>(), out[7].data_ptr<float>(), out[8].data_ptr<float>(),
+                          nb_r, out[6].data_ptr<float>(), out[7].data_ptr<float>(), out[8].data_ptr<float>(),
                           out[9].data_ptr<float>(), pr, pr ? (int)partial_r->size(0) : 0, ws.data_ptr<float>(),
                           cur_stream(x)),
         "bn_fwd_dual");
@@ -522,21 +531,17 @@ std::vector<at::Tensor> bn_bwd_dual(const at::Tensor& dy, const at::Tensor& x, c
   const int64_t M = bn_rows(x, C);
   TORCH_CHECK(r.sizes() == x.sizes() && r.strides() == x.strides() && r.scalar_type() == x.scalar_type(),
               "bn_bwd_dual: residual layout");
-  TORCH_CHECK(mask.numel() == x.numel() / 8, "bn_bwd_dual: ReLU bit mask required");
+  const uint8_t* mk = mask_ptr(mask, x.numel(), "bn_bwd_dual");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  at::Tensor dyc = dy;
-  if (dy.strides() != x.strides() || dy.scalar_type() != x.scalar_type()) {
-    dyc = at::empty_like(x);
-    dyc.copy_(dy);
-  }
+  at::Tensor dyc = dy_like(dy, x);
   auto fo = x.options().dtype(at::kFloat);
   std::vector<at::Tensor> out{at::empty_like(x), at::empty_like(x), at::empty({C}, fo), at::empty({C}, fo),
                               at::empty({C}, fo), at::empty({C}, fo)};
   at::Tensor coef = at::empty({6 * C}, fo);
   at::Tensor ws = at::empty({(int64_t)madnn_bn_partial_rows(M, (int)C) * 3 * C}, fo);
-  check(madnn_bn_bwd_dual(dyc.data_ptr(), x.data_ptr(), r.data_ptr(), mask.data_ptr<uint8_t>(), out[0].data_ptr(),
-                          out[1].data_ptr(), M, (int)C, optf(w), save_mean.data_ptr<float>(),
-                          save_invstd.data_ptr<float>(), optf(w_r), save_mean_r.data_ptr<float>(),
+  check(madnn_bn_bwd_dual(dyc.data_ptr(), x.data_ptr(), r.data_ptr(), mk, out[0].data_ptr(), out[1].data_ptr(), M,
+                          (int)C, optf(w), save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), optf(w_r),
+                          save_mean_r.data_ptr<float>(),
                           save_invstd_r.data_ptr<float>(), out[2].data_ptr<float>(), out[3].data_ptr<float>(),
                           out[4].data_ptr<float>(), out[5].data_ptr<float>(), coef.data_ptr<float>(),
                           ws.data_ptr<float>(), cur_stream(x)),
@@ -559,14 +564,13 @@ std::vector<at::Tensor> bn_bwd_dual_coef(const at::Tensor& dy, const at::Tensor&
               "bn_bwd_dual_coef: residual layout");
   TORCH_CHECK(dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type(),
               "bn_bwd_dual_coef: dy / x of one layout");
-  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() == x.numel() / 8,
-              "bn_bwd_dual_coef: ReLU bit mask required");
+  const uint8_t* mk = mask_ptr(mask, x.numel(), "bn_bwd_dual_coef");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto fo = x.options().dtype(at::kFloat);
   std::vector<at::Tensor> out{at::empty({6, C}, fo), at::empty({C}, fo), at::empty({C}, fo), at::empty({C}, fo),
                               at::empty({C}, fo)};
   at::Tensor ws = at::empty({(int64_t)madnn_bn_partial_rows(M, (int)C) * 3 * C}, fo);
-  check(madnn_bn_bwd_dual_coef(dy.data_ptr(), x.data_ptr(), r.data_ptr(), mask.data_ptr<uint8_t>(), M, (int)C, optf(w),
+  check(madnn_bn_bwd_dual_coef(dy.data_ptr(), x.data_ptr(), r.data_ptr(), mk, M, (int)C, optf(w),
                                save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), optf(w_r),
                                save_mean_r.data_ptr<float>(), save_invstd_r.data_ptr<float>(),
                                out[1].data_ptr<float>(), out[2].data_ptr<float>(), out[3].data_ptr<float>(),
@@ -592,24 +596,14 @@ std::vector<at::Tensor> bn_coef(const at::Tensor& x, const c10::optional<at::Ten
   auto fo = x.options().dtype(at::kFloat);
   std::vector<at::Tensor> out;
   for (int k = 0; k < 4; ++k) out.push_back(at::empty({C}, fo));
-  const bool ext = partial.has_value() && partial->defined() && partial->numel() > 0;
-  if (ext) {
-    TORCH_CHECK(partial->scalar_type() == at::kFloat && partial->is_contiguous() && partial->dim() == 3 &&
-                    partial->size(1) == 2 && partial->size(2) == C,
-                "bn: partial statistics must be fp32 [rows, 2, C]");
-  }
+  const float* ext = partial_ptr(partial, C, "bn_coef");
   at::Tensor ws = at::empty({ext ? (int64_t)madnn_bn_prereduce_floats((int)C)
                                 : (int64_t)madnn_bn_partial_rows(M, (int)C) * 2 * C},
                             fo);
-  int64_t* nb = nullptr;
-  if (nbt.has_value() && nbt->defined()) {
-    TORCH_CHECK(nbt->scalar_type() == at::kLong && nbt->is_cuda(), "num_batches_tracked must be an int64 device tensor");
-    nb = nbt->data_ptr<int64_t>();
-  }
   check(madnn_bn_coef(x.data_ptr(), M, (int)C, (float)eps, (float)momentum, optf(w), optf(b), optf_mut(run_mean),
-                      optf_mut(run_var), nb, out[0].data_ptr<float>(), out[1].data_ptr<float>(),
+                      optf_mut(run_var), nbt_ptr(nbt, "bn_coef"), out[0].data_ptr<float>(), out[1].data_ptr<float>(),
                       out[2].data_ptr<float>(), out[3].data_ptr<float>(), ws.data_ptr<float>(),
-                      ext ? partial->data_ptr<float>() : nullptr, ext ? (int)partial->size(0) : 0, cur_stream(x)),
+                      ext, ext ? (int)partial->size(0) : 0, cur_stream(x)),
         "bn_coef");
   return out;
 }
@@ -675,13 +669,10 @@ at::Tensor conv1x1_dgrad(const at::Tensor& dy, const at::Tensor& w, const c10::o
     TORCH_CHECK(conv_rows(*res, cin, "res") == M && res->dim() == dy.dim(), "conv1x1_dgrad: residual layout");
   }
   const bool has_mask = resmask.has_value() && resmask->defined();
-  if (has_mask) {
-    TORCH_CHECK(has_res && resmask->scalar_type() == at::kByte && resmask->is_contiguous() &&
-                    resmask->numel() == M * cin / 8, "conv1x1_dgrad: resmask must be a uint8 bit mask over res");
-  }
+  TORCH_CHECK(has_res || !has_mask, "conv1x1_dgrad: resmask needs res");
   check(madnn_conv1x1_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), has_res ? res->data_ptr() : nullptr, M, cin,
                             cout, nullptr, nullptr, nullptr, nullptr, cur_stream(dy),
-                            has_mask ? resmask->data_ptr<uint8_t>() : nullptr),
+                            has_mask ? mask_ptr(resmask, M * cin, "conv1x1_dgrad") : nullptr),
         "conv1x1_dgrad");
   return dx;
 }
@@ -694,14 +685,13 @@ std::tuple<at::Tensor, at::Tensor> conv1x1_dgrad_bnb(const at::Tensor& dy, const
   const int64_t M = conv_rows(dy, cout, "dy");
   conv_check_w(w, cout, cin);
   TORCH_CHECK(conv_rows(bny, cin, "bny") == M && bny.dim() == dy.dim(), "conv1x1_dgrad_bnb: bny layout");
-  TORCH_CHECK(scale.numel() == cin && shift.numel() == cin && scale.scalar_type() == at::kFloat &&
-                  shift.scalar_type() == at::kFloat && scale.is_contiguous() && shift.is_contiguous(),
-              "conv1x1_dgrad_bnb: fp32 [Cin] scale / shift");
+  const float* sc = vec_ptr(scale, cin, "conv1x1_dgrad_bnb", "scale");
+  const float* sh = vec_ptr(shift, cin, "conv1x1_dgrad_bnb", "shift");
   at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
   at::Tensor dx = conv_out_like(dy, cin);
   at::Tensor part = at::empty({madnn_conv1x1_dgrad_rows(M, cin, cout), 2, cin}, dy.options().dtype(at::kFloat));
-  check(madnn_conv1x1_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), nullptr, M, cin, cout, bny.data_ptr(),
-                            scale.data_ptr<float>(), shift.data_ptr<float>(), part.data_ptr<float>(), cur_stream(dy)),
+  check(madnn_conv1x1_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), nullptr, M, cin, cout, bny.data_ptr(), sc, sh,
+                            part.data_ptr<float>(), cur_stream(dy)),
         "conv1x1_dgrad_bnb");
   return {dx, part};
 }
@@ -731,13 +721,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_bwd_coef(const at::Tensor& dy,
   const int64_t C = x.size(1);
   const int64_t M = bn_rows(x, C);
   TORCH_CHECK(dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type(), "bn_bwd_coef: dy / x of one layout");
-  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() == x.numel() / 8,
-              "bn_bwd_coef: ReLU bit mask required");
+  const uint8_t* mk = mask_ptr(mask, x.numel(), "bn_bwd_coef");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto fo = x.options().dtype(at::kFloat);
   at::Tensor dw = at::empty({C}, fo), db = at::empty({C}, fo), coef = at::empty({3, C}, fo);
   at::Tensor ws = at::empty({(int64_t)madnn_bn_partial_rows(M, (int)C) * 2 * C}, fo);
-  check(madnn_bn_bwd_coef(dy.data_ptr(), x.data_ptr(), mask.data_ptr<uint8_t>(), 1, M, (int)C, dt_code(x), 1, optf(w),
+  check(madnn_bn_bwd_coef(dy.data_ptr(), x.data_ptr(), mk, 1, M, (int)C, dt_code(x), 1, optf(w),
                           save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(), scale.data_ptr<float>(),
                           shift.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(), coef.data_ptr<float>(),
                           ws.data_ptr<float>(), cur_stream(x)),
@@ -771,17 +760,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn3_conv3_bwd(const at::Tensor& d
     TORCH_CHECK(conv_rows(*y2, c, "y2") == M && y2->dim() == y3.dim(), "bn3_conv3_bwd: y2 layout");
   }
   conv_check_w(w3, c4, c);
-  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.is_contiguous() && mask.numel() == M * c4 / 8,
-              "bn3_conv3_bwd: ReLU bit mask over y3 required");
+  const uint8_t* mk = mask_ptr(mask, M * c4, "bn3_conv3_bwd");
   TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * c4,
               "bn3_conv3_bwd: fp32 [3, 4C] coefficients");
-  if (bnb) {
-    check_dev(*scale2, "scale2");
-    check_dev(*shift2, "shift2");
-    TORCH_CHECK(scale2->numel() == c && shift2->numel() == c && scale2->scalar_type() == at::kFloat &&
-                    shift2->scalar_type() == at::kFloat && scale2->is_contiguous() && shift2->is_contiguous(),
-                "bn3_conv3_bwd: fp32 [C] scale / shift");
-  }
+  const float* sc2 = bnb ? vec_ptr(*scale2, c, "bn3_conv3_bwd", "scale2") : nullptr;
+  const float* sh2 = bnb ? vec_ptr(*shift2, c, "bn3_conv3_bwd", "shift2") : nullptr;
   at::hip::HIPGuardMasqueradingAsCUDA guard(y3.device());
   auto fo = y3.options().dtype(at::kFloat);
   const int64_t groups = madnn_bn3_conv3_bwd_groups(M);
@@ -789,11 +772,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn3_conv3_bwd(const at::Tensor& d
   at::Tensor part = at::empty({bnb ? groups : 0, 2, c}, fo);
   at::Tensor slabs = at::empty({groups, c4, c}, fo);
   at::Tensor dw = at::empty({c4, c}, y3.options().dtype(dw_bf16 ? at::kBFloat16 : at::kFloat));
-  check(madnn_bn3_conv3_bwd(dout.data_ptr(), y3.data_ptr(), mask.data_ptr<uint8_t>(), coef.data_ptr<float>(),
-                            w3.data_ptr(), a2.data_ptr(), bnb ? y2->data_ptr() : nullptr,
-                            bnb ? scale2->data_ptr<float>() : nullptr, bnb ? shift2->data_ptr<float>() : nullptr,
-                            da2.data_ptr(), bnb ? part.data_ptr<float>() : nullptr, slabs.data_ptr<float>(),
-                            dw.data_ptr(), dw_bf16 ? 1 : 0, M, c, c4, cur_stream(y3)),
+  check(madnn_bn3_conv3_bwd(dout.data_ptr(), y3.data_ptr(), mk, coef.data_ptr<float>(), w3.data_ptr(), a2.data_ptr(),
+                            bnb ? y2->data_ptr() : nullptr, sc2, sh2, da2.data_ptr(),
+                            bnb ? part.data_ptr<float>() : nullptr, slabs.data_ptr<float>(), dw.data_ptr(),
+                            dw_bf16 ? 1 : 0, M, c, c4, cur_stream(y3)),
         "bn3_conv3_bwd");
   return {da2, part, dw};
 }
@@ -989,14 +971,18 @@ std::tuple<at::Tensor, at::Tensor> linear_dgrad_p(const at::Tensor& dy, const at
 // ---- K13 NHWC 3x3 / stride 1 / pad 1 convolution on MFMA --------------------------------------
 // x: [N, Ci, H, W] channels_last bf16; w: [Co, Ci, 3, 3] channels_last ([Co][3][3][Ci] in memory).
 // stride 2 / pad 1 (K13 SD = 2): y [N, Co, H/2, W/2] channels_last (+ BN statistics partial rows)
-std::tuple<at::Tensor, at::Tensor> conv3x3_fwd_s2(const at::Tensor& x, const at::Tensor& w, bool stats) {
+void conv3_check(const at::Tensor& x, const at::Tensor& w, const char* op) {
   check_dev(x, "x");
   check_dev(w, "w");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "conv3x3_s2: bf16 only");
-  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast), "conv3x3_s2: x must be NHWC 4-D");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, op, ": bf16 only");
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": x must be NHWC 4-D");
   TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == x.size(1) &&
                   w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3_s2: w must be a channels_last [Co, Ci, 3, 3]");
+              op, ": w must be a channels_last [Co, Ci, 3, 3]");
+}
+
+std::tuple<at::Tensor, at::Tensor> conv3x3_fwd_s2(const at::Tensor& x, const at::Tensor& w, bool stats) {
+  conv3_check(x, w, "conv3x3_s2");
   const int N = (int)x.size(0), Ci = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3), Co = (int)w.size(0);
   TORCH_CHECK(madnn_conv3x3_s2_supported(H, W, Ci, Co), "conv3x3_s2: unsupported shape Ci=", Ci, " Co=", Co, " H=", H,
               " W=", W);
@@ -1011,13 +997,7 @@ std::tuple<at::Tensor, at::Tensor> conv3x3_fwd_s2(const at::Tensor& x, const at:
 }
 
 std::tuple<at::Tensor, at::Tensor> conv3x3_fwd(const at::Tensor& x, const at::Tensor& w, bool stats) {
-  check_dev(x, "x");
-  check_dev(w, "w");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "conv3x3: bf16 only");
-  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast), "conv3x3: x must be NHWC 4-D");
-  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == x.size(1) &&
-                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3: w must be a channels_last [Co, Ci, 3, 3]");
+  conv3_check(x, w, "conv3x3");
   const int N = (int)x.size(0), Ci = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3), Co = (int)w.size(0);
   TORCH_CHECK(madnn_conv3x3_supported(H, W, Ci, Co), "conv3x3: unsupported shape Ci=", Ci, " Co=", Co, " W=", W);
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
@@ -1034,29 +1014,21 @@ std::tuple<at::Tensor, at::Tensor> conv3x3_fwd(const at::Tensor& x, const at::Te
 // bny (the BN input feeding relu -> this conv) in the epilogue: -> (dx, partial [rows, 2, Co])
 std::tuple<at::Tensor, at::Tensor> conv3x3_fwd_bnb(const at::Tensor& x, const at::Tensor& w, const at::Tensor& bny,
                                                    const at::Tensor& scale, const at::Tensor& shift) {
-  check_dev(x, "x");
-  check_dev(w, "w");
+  conv3_check(x, w, "conv3x3");
   check_dev(bny, "bny");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16 &&
-                  bny.scalar_type() == at::kBFloat16,
-              "conv3x3: bf16 only");
-  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast), "conv3x3: x must be NHWC 4-D");
-  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3 && w.size(1) == x.size(1) &&
-                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3: w must be a channels_last [Co, Ci, 3, 3]");
+  TORCH_CHECK(bny.scalar_type() == at::kBFloat16, "conv3x3: bf16 only");
   const int N = (int)x.size(0), Ci = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3), Co = (int)w.size(0);
   TORCH_CHECK(bny.dim() == 4 && bny.size(0) == N && bny.size(1) == Co && bny.size(2) == H && bny.size(3) == W &&
                   bny.is_contiguous(at::MemoryFormat::ChannelsLast),
               "conv3x3_fwd_bnb: bny must be the NHWC [N, Co, H, W] BN input");
-  TORCH_CHECK(scale.numel() == Co && shift.numel() == Co && scale.scalar_type() == at::kFloat &&
-                  shift.scalar_type() == at::kFloat && scale.is_contiguous() && shift.is_contiguous(),
-              "conv3x3_fwd_bnb: fp32 [Co] scale / shift");
+  const float* sc = vec_ptr(scale, Co, "conv3x3_fwd_bnb", "scale");
+  const float* sh = vec_ptr(shift, Co, "conv3x3_fwd_bnb", "shift");
   TORCH_CHECK(madnn_conv3x3_supported(H, W, Ci, Co), "conv3x3: unsupported shape Ci=", Ci, " Co=", Co, " W=", W);
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   at::Tensor y = at::empty({N, Co, H, W}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
   at::Tensor part = at::empty({madnn_conv3x3_stat_rows((int64_t)N * H * W), 2, Co}, x.options().dtype(at::kFloat));
-  check(madnn_conv3x3_fwd_bnb(x.data_ptr(), w.data_ptr(), y.data_ptr(), part.data_ptr<float>(), bny.data_ptr(),
-                              scale.data_ptr<float>(), shift.data_ptr<float>(), N, H, W, Ci, Co, cur_stream(x)),
+  check(madnn_conv3x3_fwd_bnb(x.data_ptr(), w.data_ptr(), y.data_ptr(), part.data_ptr<float>(), bny.data_ptr(), sc, sh,
+                              N, H, W, Ci, Co, cur_stream(x)),
         "conv3x3_fwd_bnb");
   return {y, part};
 }
