@@ -34,7 +34,8 @@ from ..nn.norm import FusedGlobalAvgPool2d, FusedMaxPool2d
 from ..ops import (batch_norm_add_bn_relu, bn2_conv3_bn3_add_bn_relu, bn2_conv3_bn3_add_bn_relu_supported,
                    bn2_conv3_bn3_add_relu, bn2_conv3_bn3_supported, bn_relu_conv1x1,
                    bn_relu_conv1x1_epi_supported, bn_relu_conv3x3, bn_relu_conv3x3_supported, bn_relu_maxpool,
-                   bn_relu_maxpool_supported, conv1x1_route, defer_res_mask)
+                   bn_relu_maxpool_supported, conv1x1_route, defer_res_mask, stem_bn_relu_maxpool,
+                   stem_bn_relu_maxpool_supported)
 
 # A/B knob: sum the downsample path's input gradient inside conv1's data grad (1) or by autograd (0)
 _FORK_DS = os.environ.get("MADNN_FORK_DOWNSAMPLE", "1") != "0"
@@ -238,7 +239,16 @@ class ResNet(nn.Module):
         layers += [block(self.inplanes, planes) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
+    def _stem_fused(self, x) -> bool:
+        """The whole stem as one node (its backward never writes conv1's output gradient): decided before any
+        kernel is issued."""
+        return (isinstance(x, torch.Tensor) and isinstance(self.conv1, FusedConv2d) and isinstance(self.bn1, BN)
+                and isinstance(self.maxpool, FusedMaxPool2d) and self.conv1.stem_ok(x)
+                and stem_bn_relu_maxpool_supported(x, self.conv1.weight, self.bn1, self.maxpool))
+
     def stem(self, x):
+        if self._stem_fused(x):
+            return stem_bn_relu_maxpool(x, self.conv1.weight, self.bn1, self.maxpool)
         y, st = self.conv1(x, stats=True)
         if isinstance(self.bn1, BN) and isinstance(self.maxpool, FusedMaxPool2d) \
                 and bn_relu_maxpool_supported(y, self.bn1, self.maxpool):

@@ -47,6 +47,10 @@ class FusedConv2d(nn.Conv2d):
                 and self.dilation == (1, 1) and self.groups == 1 and self.bias is None
                 and ops.stem_supported(x, self.weight))
 
+    def stem_ok(self, x: torch.Tensor) -> bool:
+        """Whether ``forward(x)`` would run on K10 (the ResNet stem geometry on a supported image)."""
+        return self._k10(x)
+
     def forward(self, x: torch.Tensor, stats: bool = False, fork: bool = False):
         """``conv(x)``.  ``stats=True`` also returns ``partial``, the batch statistics of ``y`` for
         :class:`~madnn.nn.FusedBatchNorm2d` (None when not computed by the kernel); ``fork=True``

@@ -1083,13 +1083,18 @@ class _BNReluMaxPoolFn(torch.autograd.Function):
         return dy, dw, db, None, None, None
 
 
-def bn_relu_maxpool_supported(y: torch.Tensor, bn, pool) -> bool:
-    """The stem shape the fused BN + ReLU + 3x3/s2 max-pool takes (training BN, bf16 NHWC)."""
-    return (_POOL_BN and isinstance(y, torch.Tensor) and y.device.type == "cuda" and y.dtype == torch.bfloat16 and y.dim() == 4
-            and y.is_contiguous(memory_format=torch.channels_last) and _bn_trainable(bn)
+def _bn_relu_maxpool_modules_ok(bn, pool) -> bool:
+    """The module half of :func:`bn_relu_maxpool_supported`: a training BatchNorm and a plain 3x3/s2 max-pool."""
+    return (_POOL_BN and _bn_trainable(bn)
             and _pair(pool.kernel_size) == (3, 3) and _pair(pool.stride) == (2, 2)
             and _pair(pool.padding) in ((1, 1), (0, 0)) and _pair(pool.dilation) == (1, 1)
-            and not pool.ceil_mode and not pool.return_indices
+            and not pool.ceil_mode and not pool.return_indices)
+
+
+def bn_relu_maxpool_supported(y: torch.Tensor, bn, pool) -> bool:
+    """The stem shape the fused BN + ReLU + 3x3/s2 max-pool takes (training BN, bf16 NHWC)."""
+    return (isinstance(y, torch.Tensor) and y.device.type == "cuda" and y.dtype == torch.bfloat16 and y.dim() == 4
+            and y.is_contiguous(memory_format=torch.channels_last) and _bn_relu_maxpool_modules_ok(bn, pool)
             and y.size(1) % 8 == 0 and 256 % (y.size(1) // 8) == 0 and y.numel() < 2 ** 31)
 
 
@@ -1348,6 +1353,59 @@ def stem_conv(x: torch.Tensor, w: torch.Tensor, *, stats: bool = False):
     _need_native("stem_conv")
     y, part = _StemFn.apply(x, w, stats)
     return (y, part) if stats else y
+
+
+class _StemBNReluMaxPoolFn(torch.autograd.Function):
+    """``max_pool2d(relu(bn1(stem_conv(x))), 3, 2, p)`` in training for an image batch that needs no gradient: the
+    whole ResNet stem as one node.  Forward: the kernels of :class:`_StemFn` and :class:`_BNReluMaxPoolFn`, with the
+    pool also writing ``yarg``, the raw stem output at each argmax.  Backward: bn1's reduction over the pooled
+    ``dp`` and ``yarg`` + finalize, then the stem weight grad that forms ``dy = ca g + cb y + cc`` on chip from
+    ``y``, ``dp`` and the argmax bytes -- ``dy``, the largest activation gradient of the network, is never written."""
+
+    @staticmethod
+    def forward(ctx, x, w, bn_w, bn_b, bn, p):
+        y, part = torch.ops.madnn.stem_fwd(x, _stem_pack(w), True)
+        mean, invstd, scale, shift = torch.ops.madnn.bn_coef(y, bn_w, bn_b, bn.running_mean, bn.running_var,
+                                                             bn.num_batches_tracked, float(bn.momentum),
+                                                             float(bn.eps), part)
+        out, arg, yarg = torch.ops.madnn.pool_bn_fwd_yarg(y, scale, shift, int(p))
+        ctx.save_for_backward(x, w, y, arg, yarg, bn_w, mean, invstd, scale, shift)
+        ctx.p = int(p)
+        return out
+
+    @staticmethod
+    def backward(ctx, dp):
+        x, w, y, arg, yarg, bn_w, mean, invstd, scale, shift = ctx.saved_tensors
+        dp = _like(dp, yarg)
+        coef, dbw, dbb = torch.ops.madnn.pool_bn_bwd_coef(dp, yarg, bn_w, mean, invstd, scale, shift,
+                                                          y.numel() // y.size(1))
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = _like(torch.ops.madnn.stem_wgrad_bnp(x, y, dp, arg, scale, shift, coef, ctx.p).to(w.dtype), w)
+        need = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        return None, dw, dbw if need else None, dbb if need else None, None, None
+
+
+_STEM_BWD_FUSED = os.environ.get("MADNN_STEM_BWD_FUSED", "1") != "0"  # A/B switch (see _StemBNReluMaxPoolFn)
+
+
+def stem_bn_relu_maxpool_supported(x: torch.Tensor, w: torch.Tensor, bn, pool) -> bool:
+    """Inputs :func:`stem_bn_relu_maxpool` takes: what :func:`stem_supported` and :func:`bn_relu_maxpool_supported`
+    ask (the latter of the stem output, 64 channels, whose shape follows from ``x``), an image batch that needs no
+    gradient, and gradients being recorded."""
+    if not (_STEM_BWD_FUSED and isinstance(x, torch.Tensor) and stem_supported(x, w) and w.size(0) == 64
+            and not x.requires_grad and torch.is_grad_enabled() and _bn_relu_maxpool_modules_ok(bn, pool)
+            and bn.weight.numel() == 64 and native_available()):
+        return False
+    ho, wo, p = (x.size(2) - 1) // 2 + 1, (x.size(3) - 1) // 2 + 1, _pair(pool.padding)[0]
+    return ho + 2 * p >= 3 and wo + 2 * p >= 3 and x.size(0) * 64 * ho * wo < 2 ** 31
+
+
+def stem_bn_relu_maxpool(x: torch.Tensor, w: torch.Tensor, bn, pool) -> torch.Tensor:
+    """``pool(relu(bn(conv2d(x, w, stride=2, padding=3))))`` (see :class:`_StemBNReluMaxPoolFn`); the caller checks
+    :func:`stem_bn_relu_maxpool_supported`."""
+    _need_native("stem_bn_relu_maxpool")
+    return _StemBNReluMaxPoolFn.apply(x, w, bn.weight, bn.bias, bn, _pair(pool.padding)[0])
 
 
 def hidden_supported(h: int) -> bool:
@@ -2008,7 +2066,7 @@ __all__ = [
     "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
     "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
     "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",
-    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "stem_conv", "stem_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
+    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "stem_conv", "stem_supported", "stem_bn_relu_maxpool", "stem_bn_relu_maxpool_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
 ]

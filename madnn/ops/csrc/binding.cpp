@@ -52,8 +52,11 @@ int madnn_maxpool_supported(int64_t, int, int);
 hipError_t madnn_maxpool_fwd(const void*, void*, void*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 int madnn_pool_bn_supported(int64_t, int);
 int madnn_pool_bn_bwd_rows(int64_t, int);
-hipError_t madnn_pool_bn_fwd(const void*, const float*, const float*, void*, void*, int, int, int, int, int, int, int,
-                             hipStream_t);
+int madnn_pool_bn_bwd_pooled_rows(int64_t, int);
+hipError_t madnn_pool_bn_fwd(const void*, const float*, const float*, void*, void*, void*, int, int, int, int, int, int,
+                             int, hipStream_t);
+hipError_t madnn_pool_bn_bwd_pooled(const void*, const void*, const float*, const float*, const float*, const float*,
+                                    const float*, float*, float*, float*, float*, int64_t, int64_t, int, hipStream_t);
 hipError_t madnn_pool_bn_bwd(const void*, const void*, const void*, const float*, const float*, const float*,
                              const float*, const float*, void*, float*, float*, float*, float*, int, int, int, int, int,
                              int, int, hipStream_t);
@@ -103,6 +106,9 @@ int madnn_stem_stat_rows(int, int, int);
 hipError_t madnn_stem_fwd(const void*, const void*, void*, float*, int, int, int, hipStream_t);
 int64_t madnn_stem_wgrad_ws(int, int, int);
 hipError_t madnn_stem_wgrad(const void*, const void*, float*, float*, int, int, int, hipStream_t);
+hipError_t madnn_stem_wgrad_bnp(const void*, const void*, const void*, const void*, const float*, const float*,
+                                const float*, const float*, const float*, float*, float*, int, int, int, int,
+                                hipStream_t);
 int madnn_gemm_supported(int64_t, int64_t, int64_t, int64_t, int64_t);
 int madnn_conv3x3_supported(int, int, int, int);
 int madnn_conv3x3_stat_rows(int64_t);
@@ -1126,6 +1132,39 @@ at::Tensor stem_wgrad(const at::Tensor& dy, const at::Tensor& x) {
   return dw;
 }
 
+// The same gradient with dy = ca*g + cb*y + cc formed inside the kernel: y the stem output, dp / arg the fused
+// pool's output gradient and argmax bytes (pool_bn_fwd), scale / shift bn1's forward pair, coef fp32 [3, 64] =
+// (ca, cb, cc).  p: the pool's padding.
+at::Tensor stem_wgrad_bnp(const at::Tensor& x, const at::Tensor& y, const at::Tensor& dp, const at::Tensor& arg,
+                          const at::Tensor& scale, const at::Tensor& shift, const at::Tensor& coef, int64_t p) {
+  stem_check_x(x);
+  check_dev(y, "y");
+  check_dev(dp, "dp");
+  check_dev(arg, "arg");
+  const int N = (int)x.size(0), H = (int)x.size(2), W = (int)x.size(3);
+  const int64_t Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  TORCH_CHECK(p >= 0 && p <= 1 && Ho + 2 * p >= 3 && Wo + 2 * p >= 3, "stem_wgrad_bnp: unsupported pool");
+  const int64_t Hp = (Ho + 2 * p - 3) / 2 + 1, Wp = (Wo + 2 * p - 3) / 2 + 1;
+  TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.dim() == 4 && y.size(0) == N && y.size(1) == 64 &&
+                  y.size(2) == Ho && y.size(3) == Wo && y.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "stem_wgrad_bnp: y must be channels_last bf16 [N, 64, Ho, Wo]");
+  TORCH_CHECK(dp.scalar_type() == at::kBFloat16 && dp.dim() == 4 && dp.size(0) == N && dp.size(1) == 64 &&
+                  dp.size(2) == Hp && dp.size(3) == Wp && dp.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "stem_wgrad_bnp: dp must be channels_last bf16 [N, 64, Hp, Wp]");
+  TORCH_CHECK(arg.scalar_type() == at::kByte && arg.is_contiguous() && arg.numel() == dp.numel(),
+              "stem_wgrad_bnp: argmax map mismatch");
+  const float* sc = vec_ptr(scale, 64, "stem_wgrad_bnp", "scale");
+  const float* sh = vec_ptr(shift, 64, "stem_wgrad_bnp", "shift");
+  const float* cf = vec_ptr(coef, 3 * 64, "stem_wgrad_bnp", "coef");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  at::Tensor ws = at::empty({madnn_stem_wgrad_ws(N, H, W)}, x.options().dtype(at::kFloat));
+  at::Tensor dw = at::empty({64, 3, 7, 7}, x.options().dtype(at::kFloat));
+  check(madnn_stem_wgrad_bnp(x.data_ptr(), y.data_ptr(), dp.data_ptr(), arg.data_ptr(), sc, sh, cf, cf + 64, cf + 128,
+                             ws.data_ptr<float>(), dw.data_ptr<float>(), N, H, W, (int)p, cur_stream(x)),
+        "stem_wgrad_bnp");
+  return dw;
+}
+
 // ---- K6 fused softmax cross-entropy ------------------------------------------
 // logits: [N, ld] or [B, S, ld] contiguous; V <= ld valid columns.  shift: causal
 // LM (logit row (b, s) predicts target (b, s+1); the last position has no loss).
@@ -1249,8 +1288,8 @@ at::Tensor maxpool_bwd(const at::Tensor& dy, const at::Tensor& arg, int64_t H, i
 
 // maxpool 3x3/s2(relu(bn(y))) with the BN apply + ReLU fused into the pool (ResNet stem).
 // y: bf16 NHWC raw BN input; scale/shift from bn_coef.  -> (pooled output, 1-byte argmax map)
-std::tuple<at::Tensor, at::Tensor> pool_bn_fwd(const at::Tensor& y, const at::Tensor& scale, const at::Tensor& shift,
-                                               int64_t p) {
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pool_bn_fwd_impl(const at::Tensor& y, const at::Tensor& scale,
+                                                                const at::Tensor& shift, int64_t p, bool want_yarg) {
   check_dev(y, "y");
   TORCH_CHECK(y.dim() == 4 && y.is_contiguous(at::MemoryFormat::ChannelsLast) && y.scalar_type() == at::kBFloat16,
               "pool_bn: bf16 NHWC 4-D input");
@@ -1264,10 +1303,55 @@ std::tuple<at::Tensor, at::Tensor> pool_bn_fwd(const at::Tensor& y, const at::Te
   at::hip::HIPGuardMasqueradingAsCUDA guard(y.device());
   at::Tensor out = at::empty({N, C, Ho, Wo}, y.options().memory_format(at::MemoryFormat::ChannelsLast));
   at::Tensor arg = at::empty({N * Ho * Wo * C}, y.options().dtype(at::kByte));
+  at::Tensor yarg = want_yarg ? at::empty_like(out) : at::Tensor();
   check(madnn_pool_bn_fwd(y.data_ptr(), scale.data_ptr<float>(), shift.data_ptr<float>(), out.data_ptr(),
-                          arg.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo, (int)p, cur_stream(y)),
+                          arg.data_ptr(), want_yarg ? yarg.data_ptr() : nullptr, (int)N, (int)H, (int)W, (int)C,
+                          (int)Ho, (int)Wo, (int)p, cur_stream(y)),
         "pool_bn_fwd");
+  return {out, arg, yarg};
+}
+
+std::tuple<at::Tensor, at::Tensor> pool_bn_fwd(const at::Tensor& y, const at::Tensor& scale, const at::Tensor& shift,
+                                               int64_t p) {
+  auto [out, arg, yarg] = pool_bn_fwd_impl(y, scale, shift, p, false);
   return {out, arg};
+}
+
+// -> (pooled output, argmax map, yarg): yarg = the raw y at each argmax, laid out as the output
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pool_bn_fwd_yarg(const at::Tensor& y, const at::Tensor& scale,
+                                                                const at::Tensor& shift, int64_t p) {
+  return pool_bn_fwd_impl(y, scale, shift, p, true);
+}
+
+// bn's backward reduction in the pooled domain + finalize -> (coef [3, C] = (ca, cb, cc), dw, db).  dp: the pool
+// output gradient; yarg from pool_bn_fwd_yarg; pixels: N * H * W of bn's input (what its statistics counted).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pool_bn_bwd_coef(const at::Tensor& dp, const at::Tensor& yarg,
+                                                                const c10::optional<at::Tensor>& w,
+                                                                const at::Tensor& mean, const at::Tensor& invstd,
+                                                                const at::Tensor& scale, const at::Tensor& shift,
+                                                                int64_t pixels) {
+  check_dev(dp, "dp");
+  check_dev(yarg, "yarg");
+  TORCH_CHECK(yarg.dim() == 4 && yarg.scalar_type() == at::kBFloat16 &&
+                  yarg.is_contiguous(at::MemoryFormat::ChannelsLast) && dp.sizes() == yarg.sizes() &&
+                  dp.strides() == yarg.strides() && dp.scalar_type() == at::kBFloat16,
+              "pool_bn_bwd_coef: dp and yarg must be channels_last bf16 of one shape");
+  const int64_t C = yarg.size(1), pooled = yarg.numel() / C;
+  TORCH_CHECK(madnn_pool_bn_supported(yarg.numel(), (int)C) && pooled > 0 && pixels > 0,
+              "pool_bn_bwd_coef: unsupported shape");
+  const float* sc = vec_ptr(scale, C, "pool_bn_bwd_coef", "scale");
+  const float* sh = vec_ptr(shift, C, "pool_bn_bwd_coef", "shift");
+  const float* mu = vec_ptr(mean, C, "pool_bn_bwd_coef", "mean");
+  const float* is = vec_ptr(invstd, C, "pool_bn_bwd_coef", "invstd");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(yarg.device());
+  auto fo = yarg.options().dtype(at::kFloat);
+  at::Tensor dw = at::empty({C}, fo), db = at::empty({C}, fo), coef = at::empty({3, C}, fo);
+  at::Tensor ws = at::empty({(int64_t)madnn_pool_bn_bwd_pooled_rows(pooled, (int)C) * 2 * C}, fo);
+  check(madnn_pool_bn_bwd_pooled(dp.data_ptr(), yarg.data_ptr(), optf(w), mu, is, sc, sh, dw.data_ptr<float>(),
+                                 db.data_ptr<float>(), coef.data_ptr<float>(), ws.data_ptr<float>(), pooled, pixels,
+                                 (int)C, cur_stream(yarg)),
+        "pool_bn_bwd_coef");
+  return {coef, dw, db};
 }
 
 // -> (dy, dw, db)
@@ -1611,6 +1695,9 @@ TORCH_LIBRARY(madnn, m) {
   m.def("conv3x3_fwd_s2(Tensor x, Tensor w, bool stats) -> (Tensor, Tensor)");
   m.def("conv3x3_wgrad(Tensor dy, Tensor x, bool out_bf16) -> Tensor");
   m.def("stem_wgrad(Tensor dy, Tensor x) -> Tensor");
+  m.def(
+      "stem_wgrad_bnp(Tensor x, Tensor y, Tensor dp, Tensor arg, Tensor scale, Tensor shift, Tensor coef, int p) -> "
+      "Tensor");
   m.def("bias_grad(Tensor dy, Tensor? pre, ScalarType bias_dtype, int gelu_kind=1) -> (Tensor, Tensor)");
   m.def("gelu_fwd(Tensor x, int kind=1) -> Tensor");
   m.def("rope_qkv_(Tensor(a!) qkv, Tensor cos, Tensor sin, int rot_heads, bool inverse) -> Tensor(a!)");
@@ -1619,6 +1706,10 @@ TORCH_LIBRARY(madnn, m) {
   m.def("swiglu_bwd(Tensor dh, Tensor gu) -> Tensor");
   m.def("maxpool_fwd(Tensor x, int k, int s, int p, bool need_arg) -> (Tensor, Tensor)");
   m.def("pool_bn_fwd(Tensor y, Tensor scale, Tensor shift, int p) -> (Tensor, Tensor)");
+  m.def("pool_bn_fwd_yarg(Tensor y, Tensor scale, Tensor shift, int p) -> (Tensor, Tensor, Tensor)");
+  m.def(
+      "pool_bn_bwd_coef(Tensor dp, Tensor yarg, Tensor? w, Tensor mean, Tensor invstd, Tensor scale, Tensor shift, "
+      "int pixels) -> (Tensor, Tensor, Tensor)");
   m.def(
       "pool_bn_bwd(Tensor dp, Tensor arg, Tensor y, Tensor? w, Tensor mean, Tensor invstd, Tensor scale, Tensor shift, "
       "int p) -> (Tensor, Tensor, Tensor)");
@@ -1663,6 +1754,8 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("xent_rescale", xent_rescale);
   m.impl("maxpool_fwd", maxpool_fwd);
   m.impl("pool_bn_fwd", pool_bn_fwd);
+  m.impl("pool_bn_fwd_yarg", pool_bn_fwd_yarg);
+  m.impl("pool_bn_bwd_coef", pool_bn_bwd_coef);
   m.impl("pool_bn_bwd", pool_bn_bwd);
   m.impl("bias_grad", bias_grad);
   m.impl("gelu_fwd", gelu_fwd);
@@ -1681,6 +1774,7 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("bn3_conv3_bwd", bn3_conv3_bwd);
   m.impl("stem_fwd", stem_fwd);
   m.impl("stem_wgrad", stem_wgrad);
+  m.impl("stem_wgrad_bnp", stem_wgrad_bnp);
   m.impl("linear_fwd", linear_fwd);
   m.impl("linear_dgrad", linear_dgrad);
   m.impl("linear_wgrad", linear_wgrad);

@@ -120,13 +120,17 @@ __device__ __forceinline__ unsigned xcd_block_id(int swz) {
 // issue all loads before the first compare, keeping 9 (forward) / 8 (backward) 16-byte
 // loads in flight per lane.  Same scan order, tie-breaking and NaN rule as above.
 // BNRELU: x is a raw BatchNorm input; every window element is relu(x * sc[c] + sh[c]) (the stem's
-// BN apply + ReLU fused into its max-pool: the normalised stem activation never reaches HBM)
-template <int XDT, bool BNRELU = false>
+// BN apply + ReLU fused into its max-pool: the normalised stem activation never reaches HBM).
+// YARG (with BNRELU): also writes the raw stored x at the chosen window position, laid out as y --
+// what the pooled-domain BN backward reduction below reads instead of gathering from x.
+template <int XDT, bool BNRELU = false, bool YARG = false>
 __global__ __launch_bounds__(256) void maxpool_k3s2_fwd_kernel(const void* __restrict__ x, void* __restrict__ y,
                                                                uint64_t* __restrict__ arg, int N, int H, int W,
                                                                int C, int Ho, int Wo, int p, int swz,
                                                                const float* __restrict__ sc = nullptr,
-                                                               const float* __restrict__ sh = nullptr) {
+                                                               const float* __restrict__ sh = nullptr,
+                                                               void* __restrict__ yarg = nullptr) {
+  static_assert(!YARG || BNRELU, "yarg is the fused stem pool's");
   const unsigned CG = (unsigned)C >> 3;
   const unsigned total = (unsigned)N * Ho * Wo * CG;
   for (unsigned idx = xcd_block_id(swz) * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(256) void maxpool_k3s2_fwd_kernel(const void* __res
         }
       }
     }
-    if constexpr (BNRELU) {
+    if constexpr (BNRELU && !YARG) {
 #pragma unroll
       for (int q = 0; q < 9; ++q) {
         if (!ok[q]) continue;
@@ -167,7 +171,7 @@ __global__ __launch_bounds__(256) void maxpool_k3s2_fwd_kernel(const void* __res
         }
       }
     }
-    float best[8];
+    float best[8], raw[8];
     unsigned char a[8];
     unsigned char first = 0;
 #pragma unroll
@@ -176,6 +180,7 @@ __global__ __launch_bounds__(256) void maxpool_k3s2_fwd_kernel(const void* __res
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       best[j] = -__builtin_inff();
+      raw[j] = 0.f;
       a[j] = first;
     }
 #pragma unroll
@@ -183,13 +188,20 @@ __global__ __launch_bounds__(256) void maxpool_k3s2_fwd_kernel(const void* __res
       if (!ok[q]) continue;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        if (v[q][j] > best[j] || __builtin_isnan(v[q][j])) {
-          best[j] = v[q][j];
+        float t = v[q][j];
+        if constexpr (YARG) {  // the raw values stay in v: same expression as the in-place form above
+          const float z = t * bs[j] + bh[j];
+          t = z > 0.f ? z : 0.f;
+        }
+        if (t > best[j] || __builtin_isnan(t)) {
+          best[j] = t;
           a[j] = (unsigned char)q;
+          if constexpr (YARG) raw[j] = v[q][j];
         }
       }
     }
     store8<XDT>(y, (int64_t)pix * C + cg * 8, best);
+    if constexpr (YARG) store8<XDT>(yarg, (int64_t)pix * C + cg * 8, raw);  // bf16 -> fp32 -> bf16 is exact
     if (arg) {
       uint64_t packed = 0;
 #pragma unroll
@@ -349,6 +361,68 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_kernel(const void* __restrict
   }
 }
 
+// The BN backward sums of maxpool_k3s2(relu(bn(y))) taken in the pooled domain.  The pool's input gradient
+// is non-zero only at argmax positions, so over the stem pixels i and the pooled elements o
+//   sum_i g_i = sum_o dp[o] m[o],   sum_i g_i y_i = sum_o dp[o] m[o] yarg[o],
+// with yarg the raw y at o's argmax (the YARG forward above) and m its ReLU bit, recomputed by the forward's
+// expression.  Streams dp and yarg (16-byte loads, 4 + 4 in flight per lane) and writes one [2][C] partial row
+// per workgroup (the format of bn.hip's backward finalize).  No atomics: bitwise repeatable for a fixed grid.
+// total = 16-byte chunks; a lane's channel group is fixed as in pool_bn_bwd_kernel.
+__global__ __launch_bounds__(256) void pool_bn_bwd_pooled_sums_kernel(const void* __restrict__ dp,
+                                                                      const void* __restrict__ yarg,
+                                                                      const float* __restrict__ sc,
+                                                                      const float* __restrict__ sh,
+                                                                      float* __restrict__ partial, unsigned total,
+                                                                      int C) {
+  __shared__ float slab[256][17];
+  const unsigned CG = (unsigned)C >> 3;
+  const unsigned cg = threadIdx.x % CG;
+  float bs[8], bh[8], s0[8], s1[8];
+  load8<kF32>(sc, cg * 8, bs);
+  load8<kF32>(sh, cg * 8, bh);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s0[j] = s1[j] = 0.f;
+  auto add = [&](const float (&g)[8], const float (&yv)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float z = yv[j] * bs[j] + bh[j];
+      const float gm = z > 0.f ? g[j] : 0.f;
+      s0[j] += gm;
+      s1[j] += gm * yv[j];
+    }
+  };
+  const unsigned stride = gridDim.x * blockDim.x;  // total < 2^28 (host: numel < 2^31), so idx + 3 * stride fits
+  unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+  for (; idx + 3 * stride < total; idx += 4 * stride) {
+    float g[4][8], yv[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      load8<kBF16>(dp, (int64_t)(idx + u * stride) * 8, g[u]);
+      load8<kBF16>(yarg, (int64_t)(idx + u * stride) * 8, yv[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) add(g[u], yv[u]);
+  }
+  for (; idx < total; idx += stride) {
+    float g[8], yv[8];
+    load8<kBF16>(dp, (int64_t)idx * 8, g);
+    load8<kBF16>(yarg, (int64_t)idx * 8, yv);
+    add(g, yv);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    slab[threadIdx.x][j] = s0[j];
+    slab[threadIdx.x][8 + j] = s1[j];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < 2 * C; c += blockDim.x) {
+    const int which = c / C, ch = c % C, g8 = ch >> 3, e = ch & 7;
+    float a = 0.f;
+    for (int r = g8; r < 256; r += (int)CG) a += slab[r][which * 8 + e];
+    partial[(int64_t)blockIdx.x * 2 * C + c] = a;
+  }
+}
+
 }  // namespace madnn
 
 using namespace madnn;
@@ -426,14 +500,20 @@ int madnn_pool_bn_supported(int64_t numel, int C) {
   return numel < (1ll << 31) && C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0;
 }
 
-// maxpool_k3s2(relu(y * scale + shift)) (bf16 NHWC): output + 1-byte argmax per element
-hipError_t madnn_pool_bn_fwd(const void* x, const float* scale, const float* shift, void* y, void* arg, int N, int H,
-                             int W, int C, int Ho, int Wo, int p, hipStream_t stream) {
+// maxpool_k3s2(relu(y * scale + shift)) (bf16 NHWC): output + 1-byte argmax per element; yarg (optional,
+// null = off): the raw input at each argmax, laid out as the output
+hipError_t madnn_pool_bn_fwd(const void* x, const float* scale, const float* shift, void* y, void* arg, void* yarg,
+                             int N, int H, int W, int C, int Ho, int Wo, int p, hipStream_t stream) {
   if (!madnn_pool_bn_supported((int64_t)N * H * W * C, C) || p > 2) return hipErrorInvalidValue;
   const int64_t work = (int64_t)N * Ho * Wo * (C / 8);
   const int grid = stream_grid(work, 256, g_pool_bn_wg[0] * kNumCU);
-  hipLaunchKernelGGL((maxpool_k3s2_fwd_kernel<kBF16, true>), dim3(grid), dim3(256), 0, stream, x, y,
-                     static_cast<uint64_t*>(arg), N, H, W, C, Ho, Wo, p, 0, scale, shift);
+  if (yarg) {
+    hipLaunchKernelGGL((maxpool_k3s2_fwd_kernel<kBF16, true, true>), dim3(grid), dim3(256), 0, stream, x, y,
+                       static_cast<uint64_t*>(arg), N, H, W, C, Ho, Wo, p, 0, scale, shift, yarg);
+  } else {
+    hipLaunchKernelGGL((maxpool_k3s2_fwd_kernel<kBF16, true>), dim3(grid), dim3(256), 0, stream, x, y,
+                       static_cast<uint64_t*>(arg), N, H, W, C, Ho, Wo, p, 0, scale, shift, nullptr);
+  }
   return hipGetLastError();
 }
 
@@ -466,6 +546,25 @@ hipError_t madnn_pool_bn_bwd(const void* dp, const void* arg, const void* y, con
   hipLaunchKernelGGL((pool_bn_bwd_kernel<1>), dim3(grid), dim3(256), 0, stream, dp, a, y, scale, shift, coef, coef + C,
                      coef + 2 * C, dy, nullptr, N, H, W, C, Ho, Wo, p);
   return hipGetLastError();
+}
+
+// partial rows the pooled-domain reduction writes (pooled = N * Hp * Wp pooled pixels)
+int madnn_pool_bn_bwd_pooled_rows(int64_t pooled, int C) { return stream_grid(pooled * (C / 8), 256, 8 * kNumCU); }
+
+// bn's weight/bias grads and backward coefficients (coef = ca, cb, cc: 3 * C floats) from the pool output
+// gradient dp and yarg, both [pooled][C] bf16: reduction + finalize.  pixels = N * H * W of bn's input.
+// workspace: madnn_pool_bn_bwd_pooled_rows * 2 * C floats.
+hipError_t madnn_pool_bn_bwd_pooled(const void* dp, const void* yarg, const float* w, const float* mean,
+                                    const float* invstd, const float* scale, const float* shift, float* dw, float* db,
+                                    float* coef, float* workspace, int64_t pooled, int64_t pixels, int C,
+                                    hipStream_t stream) {
+  if (!madnn_pool_bn_supported(pooled * C, C) || pooled <= 0) return hipErrorInvalidValue;
+  const int G = madnn_pool_bn_bwd_pooled_rows(pooled, C);
+  hipLaunchKernelGGL(pool_bn_bwd_pooled_sums_kernel, dim3(G), dim3(256), 0, stream, dp, yarg, scale, shift, workspace,
+                     (unsigned)(pooled * (C / 8)), C);
+  MADNN_HIP_CHECK(hipGetLastError());
+  return madnn_bn_bwd_finalize(workspace, G, C, 2 * C, C, pixels, w, mean, invstd, dw, db, coef, coef + C,
+                               coef + 2 * C, stream);
 }
 
 }  // extern "C"

@@ -216,6 +216,15 @@ inline int stem_grid(int rows) { return rows < 2 * kNumCU ? rows : 2 * kNumCU; }
 // row r + 1 are issued before row r's MFMAs.  Wave w owns channel block b = w & 1 and the kh
 // tiles w >> 1, +2, +4, +6; accumulators stay in registers for the whole range and are written
 // once to a per-workgroup partial, summed by stem_wgrad_reduce (deterministic, no atomics).
+//
+// BNP: dy is not read but formed here, dy = ca*g + cb*y + cc rounded to bf16, the value
+// pool.hip's pool_bn_bwd_kernel<1> would have stored: g is the max-pool gradient gathered from
+// the (at most 2 x 2) pooled pixels whose windows hold the stem pixel, masked by bn1's ReLU
+// recomputed from y.  The y row takes dy's place in the staging registers.  A stem row oh needs
+// the pooled rows (oh + p) / 2 and, for even oh + p, the one above; consecutive rows share them,
+// so dp + argmax rows live in a 2-slot LDS ring (slot = pooled row & 1) and at most one new
+// pooled row is staged per stem row.  The A tile is then built from the y registers and the ring
+// (one more barrier per row); everything after the tile is shared.
 constexpr int kWMaxTiles = 4;
 
 struct StemWArgs {
@@ -224,6 +233,16 @@ struct StemWArgs {
   float* ws;           // [gridDim.x][64][3][7][7]
   int N, H, W, Ho, Wo;
   int rows, per;       // output rows, rows per workgroup
+  // BNP only (dy is formed on chip, see stem_wgrad_kernel):
+  const uint16_t* y;   // [N][Ho][Wo][64] the stem output = bn1's input
+  const uint16_t* dp;  // [N][Hp][Wp][64] gradient of the 3x3 / stride-2 max-pool's output
+  const uint64_t* arg; // [N][Hp][Wp][8] the pool's window position per element, 8 bytes per channel group
+  const float* sc;     // [64] each: bn1's forward scale / shift, its backward coefficients
+  const float* sh;
+  const float* ca;
+  const float* cb;
+  const float* cc;
+  int Hp, Wp, p;       // pooled size, pool padding
 };
 
 // B fragment: element j of lane half h = patch[ow0 + 8h + j][4 kw + c], kw = 4 (g & 1) + (i & 3)
@@ -239,13 +258,22 @@ __device__ __forceinline__ bf16x8 lds_patch(const uint16_t* img_row, int ow0, in
   return __builtin_bit_cast(bf16x8, r);
 }
 
+template <bool BNP>
 __global__ __launch_bounds__(kThreads, 2) void stem_wgrad_kernel(const StemWArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
   const int WOP = (a.Wo + 15) & ~15;          // pixels padded to the MFMA reduction step
   const int ROW = (2 * WOP + 6) * 4;          // bf16 per staged input row (>= the padded image row)
   uint16_t* ring = smem;                      // [9][ROW]; slot 8 stays zero
   uint16_t* dyt = smem + 9 * ROW;             // [WOP][64], swz<64> rows
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hh = lane >> 5, l32 = lane & 31;
+  // BNP: pooled-row ring (dp [2][Wp][64] bf16, argmax [2][Wp][8] x 8 bytes) and the five [64] fp32 vectors
+  const int pchunks = BNP ? a.Wp * 8 : 0;     // 16-B dp chunks = 8-B argmax groups of one pooled row
+  uint16_t* pdp = dyt + WOP * kCo;
+  uint64_t* parg = reinterpret_cast<uint64_t*>(pdp + 2 * pchunks * 8);
+  float* cf = reinterpret_cast<float*>(parg + 2 * pchunks);
+  // BNP: the staging lambdas make tid opaque to the compiler per call, or the row loop keeps every chunk's
+  // loop-invariant addresses in registers from row to row and spills
+  int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63, hh = lane >> 5, l32 = lane & 31;
   const int row_elems = a.W * 3, chunks = row_elems / 8;
   const int dchunks = a.Wo * 8;               // 16-B chunks of one dy row
 
@@ -261,11 +289,46 @@ __global__ __launch_bounds__(kThreads, 2) void stem_wgrad_kernel(const StemWArgs
 
   u32x4 istg[4], dstg[4];
   int s_oh = 0, s_klo = 0;                    // row being staged: output row and first new kh
+  u32x4 pstg[2];                              // BNP: the pooled row being staged (Wp <= 64: 2 chunks per thread)
+  u32x2 astg[2];
+  int s_pslot = -1;                           // its ring slot, -1 = none
+  auto pload = [&](int n, int ohp) {
+    if constexpr (BNP) asm volatile("" : "+v"(tid));
+    s_pslot = ohp & 1;
+    const int64_t base = ((int64_t)n * a.Hp + ohp) * pchunks;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + kThreads * i;
+      if (c < pchunks) {
+        pstg[i] = *reinterpret_cast<const u32x4*>(a.dp + (base + c) * 8);
+        astg[i] = *reinterpret_cast<const u32x2*>(a.arg + base + c);
+      }
+    }
+  };
+  auto pstore = [&]() {
+    if (s_pslot < 0) return;
+    if constexpr (BNP) asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + kThreads * i;
+      if (c < pchunks) {
+        *reinterpret_cast<u32x4*>(pdp + (s_pslot * pchunks + c) * 8) = pstg[i];
+        *reinterpret_cast<u32x2*>(parg + s_pslot * pchunks + c) = astg[i];
+      }
+    }
+  };
   auto load = [&](int r) {
+    if constexpr (BNP) asm volatile("" : "+v"(tid));
     const int n = r / a.Ho, oh = r % a.Ho;
     const bool fresh = (r == r0) || (oh == 0);
     s_oh = oh;
     s_klo = fresh ? 0 : 5;
+    if constexpr (BNP) {
+      // pooled row (oh + p) / 2 is new when oh + p is even (the row above it was staged for an earlier oh)
+      const int h1 = (oh + a.p) >> 1;
+      s_pslot = -1;
+      if ((fresh || ((oh + a.p) & 1) == 0) && h1 < a.Hp) pload(n, h1);
+    }
     const int total = (kKh - s_klo) * chunks;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -277,10 +340,12 @@ __global__ __launch_bounds__(kThreads, 2) void stem_wgrad_kernel(const StemWArgs
           istg[i] = *reinterpret_cast<const u32x4*>(a.x + ((int64_t)n * a.H + ih) * row_elems + (c % chunks) * 8);
       }
       const int d = tid + kThreads * i;
-      if (d < dchunks) dstg[i] = *reinterpret_cast<const u32x4*>(a.dy + ((int64_t)r * a.Wo) * kCo + d * 8);
+      if (d < dchunks)
+        dstg[i] = *reinterpret_cast<const u32x4*>((BNP ? a.y : a.dy) + ((int64_t)r * a.Wo) * kCo + d * 8);
     }
   };
   auto store = [&]() {
+    if constexpr (BNP) asm volatile("" : "+v"(tid));
     const int total = (kKh - s_klo) * chunks;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -296,16 +361,99 @@ __global__ __launch_bounds__(kThreads, 2) void stem_wgrad_kernel(const StemWArgs
           }
         }
       }
+      if constexpr (!BNP) {
+        const int d = tid + kThreads * i;
+        if (d < dchunks)
+          *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(dyt) + swz<64>(d >> 3, d & 7)) = dstg[i];
+      }
+    }
+    if constexpr (BNP) pstore();
+  };
+  // BNP: the staged row's A tile from its y registers and the pooled ring.  Window arithmetic, summation
+  // order over the pooled pixels, mask and affine form are pool_bn_bwd_kernel<1>'s (pool.hip).
+  auto build = [&]() {
+    const int hp = s_oh + a.p, h1 = hp >> 1, hodd = hp & 1;
+    const bool okh[2] = {hodd == 0 && h1 >= 1, h1 < a.Hp};   // pooled rows h1 - 1 (window row 2), h1 (row hodd)
+    if constexpr (BNP) asm volatile("" : "+v"(tid));
+    const int cg = tid & 7;                                   // fixed: kThreads % 8 == 0
+    float v[5][8];                                            // scale, shift, ca, cb, cc of this channel group
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(cf + k * kCo + cg * 8);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(cf + k * kCo + cg * 8 + 4);
+      v[k][0] = lo.x; v[k][1] = lo.y; v[k][2] = lo.z; v[k][3] = lo.w;
+      v[k][4] = hi.x; v[k][5] = hi.y; v[k][6] = hi.z; v[k][7] = hi.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
       const int d = tid + kThreads * i;
-      if (d < dchunks)
-        *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(dyt) + swz<64>(d >> 3, d & 7)) = dstg[i];
+      if (d < dchunks) {
+        const int wp = (d >> 3) + a.p, w1 = wp >> 1, wodd = wp & 1;
+        const bool okw[2] = {wodd == 0 && w1 >= 1, w1 < a.Wp};
+        u32x4 g[4];
+        u32x2 pk[4];
+        bool ok[4];
+        unsigned pos[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int ih = q >> 1, iw = q & 1;
+          ok[q] = okh[ih] && okw[iw];
+          pos[q] = (unsigned)((ih ? hodd : 2) * 3 + (iw ? wodd : 2));
+          // unconditional reads (all four in flight); a pixel that is not ok reads a clamped address
+          const int ow = min(max(w1 - 1 + iw, 0), a.Wp - 1);
+          const int c = (((h1 - 1 + ih) & 1) * a.Wp + ow) * 8 + cg;
+          g[q] = *reinterpret_cast<const u32x4*>(pdp + c * 8);
+          pk[q] = *reinterpret_cast<const u32x2*>(parg + c);
+        }
+        u32x4 o4;
+#pragma unroll
+        for (int j2 = 0; j2 < 4; ++j2) {
+          unsigned short ob[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int j = 2 * j2 + e;
+            float acc = 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const float gj = bf16_to_f32((unsigned short)((g[q][j >> 1] >> (16 * (j & 1))) & 0xffffu));
+              const unsigned byte = (pk[q][j >> 2] >> (8 * (j & 3))) & 0xffu;
+              if (ok[q]) acc += (byte == pos[q]) ? gj : 0.f;
+            }
+            const float yv = bf16_to_f32((unsigned short)((dstg[i][j >> 1] >> (16 * (j & 1))) & 0xffffu));
+            const float z = yv * v[0][j] + v[1][j];
+            acc = z > 0.f ? acc : 0.f;
+            ob[e] = f32_to_bf16(v[2][j] * acc + v[3][j] * yv + v[4][j]);
+          }
+          o4[j2] = (unsigned)ob[0] | ((unsigned)ob[1] << 16);
+        }
+        *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(dyt) + swz<64>(d >> 3, d & 7)) = o4;
+      }
+      __builtin_amdgcn_sched_barrier(0);  // one chunk's gather at a time: hoisting all four spills registers
     }
   };
 
+  if constexpr (BNP) {
+    for (int i = tid; i < 5 * kCo; i += kThreads) {
+      const float* src = i < kCo ? a.sc : i < 2 * kCo ? a.sh : i < 3 * kCo ? a.ca : i < 4 * kCo ? a.cb : a.cc;
+      cf[i] = src[i % kCo];
+    }
+  }
   __syncthreads();  // zeroed
+  if constexpr (BNP) {
+    // a range that starts on an even oh + p also needs the pooled row above the one load() stages
+    const int n = r0 / a.Ho, hp = r0 % a.Ho + a.p;
+    if ((hp & 1) == 0 && (hp >> 1) >= 1) {
+      pload(n, (hp >> 1) - 1);
+      pstore();
+    }
+  }
   load(r0);
   store();
   __syncthreads();
+  if constexpr (BNP) {
+    build();
+    __syncthreads();
+  }
   for (int r = r0;;) {
     const int oh = r % a.Ho;
     const bool more = r + 1 < r1;
@@ -326,6 +474,10 @@ __global__ __launch_bounds__(kThreads, 2) void stem_wgrad_kernel(const StemWArgs
     __syncthreads();  // every wave done with dyt and the ring slots being replaced
     store();
     __syncthreads();
+    if constexpr (BNP) {
+      build();
+      __syncthreads();
+    }
     ++r;
   }
 
@@ -444,7 +596,48 @@ hipError_t madnn_stem_wgrad(const void* x, const void* dy, float* ws, float* dw,
   const int grid = (a.rows + a.per - 1) / a.per;  // every workgroup owns >= 1 row (writes its partial)
   const int WOP = (a.Wo + 15) & ~15;
   const size_t lds = (size_t)(9 * (2 * WOP + 6) * 4 + WOP * kCo) * sizeof(uint16_t);
-  hipLaunchKernelGGL(stem_wgrad_kernel, dim3(grid), dim3(kThreads), lds, s, a);
+  hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(grid), dim3(kThreads), lds, s, a);
+  MADNN_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(stem_wgrad_reduce, dim3((kCo * 147 + 31) / 32), dim3(256), 0, s, ws, dw, grid);
+  return hipGetLastError();
+}
+
+// The weight gradient with bn1's backward apply and the 3x3 / stride-2 max-pool's backward formed on chip:
+// y [N][Ho][Wo][64] the stem output, dp [N][Hp][Wp][64] the pool's output gradient, arg its argmax bytes
+// (pool.hip), scale/shift bn1's forward pair, ca/cb/cc its backward coefficients ([64] fp32 each).
+hipError_t madnn_stem_wgrad_bnp(const void* x, const void* y, const void* dp, const void* arg, const float* scale,
+                                const float* shift, const float* ca, const float* cb, const float* cc, float* ws,
+                                float* dw, int N, int H, int W, int p, hipStream_t s) {
+  if (!madnn_stem_supported(H, W) || p < 0 || p > 1) return hipErrorInvalidValue;
+  StemWArgs a{};
+  a.x = static_cast<const uint16_t*>(x);
+  a.y = static_cast<const uint16_t*>(y);
+  a.dp = static_cast<const uint16_t*>(dp);
+  a.arg = static_cast<const uint64_t*>(arg);
+  a.sc = scale;
+  a.sh = shift;
+  a.ca = ca;
+  a.cb = cb;
+  a.cc = cc;
+  a.ws = ws;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.Ho = (H + 6 - 7) / 2 + 1;
+  a.Wo = (W + 6 - 7) / 2 + 1;
+  a.p = p;
+  a.Hp = (a.Ho + 2 * p - 3) / 2 + 1;
+  a.Wp = (a.Wo + 2 * p - 3) / 2 + 1;
+  if (a.Ho + 2 * p < 3 || a.Wo + 2 * p < 3) return hipErrorInvalidValue;
+  a.rows = N * a.Ho;
+  if (a.rows <= 0) return hipMemsetAsync(dw, 0, sizeof(float) * kCo * 147, s);
+  a.per = (a.rows + wgrad_grid(a.rows) - 1) / wgrad_grid(a.rows);
+  const int grid = (a.rows + a.per - 1) / a.per;
+  const int WOP = (a.Wo + 15) & ~15;
+  // Wo <= 128 gives Wp <= 64: at most 61104 bytes
+  const size_t lds = (size_t)(9 * (2 * WOP + 6) * 4 + WOP * kCo) * sizeof(uint16_t) + (size_t)2 * a.Wp * kCo * 3 +
+                     5 * kCo * sizeof(float);
+  hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(grid), dim3(kThreads), lds, s, a);
   MADNN_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(stem_wgrad_reduce, dim3((kCo * 147 + 31) / 32), dim3(256), 0, s, ws, dw, grid);
   return hipGetLastError();
