@@ -1,8 +1,9 @@
 """Shared transformer pieces.
 
 Attention on the GPU is madnn's K8 MFMA flash-attention kernel, reading the packed
-QKV projection in place ([B, S, heads, D], no transposes); elsewhere (CPU, dropout,
-other head dims) ``F.scaled_dot_product_attention``.  QKV is one fused projection
+QKV projection in place ([B, S, heads, D], no transposes), attention dropout
+included (in-kernel Philox mask); elsewhere (CPU, other head dims, dropout with
+``MADNN_ATTN_DROPOUT=0`` or under stream capture) ``F.scaled_dot_product_attention``.  QKV is one fused projection
 GEMM (hipBLASLt); norms are the madnn K3 kernel with the residual add fused in.
 
 Every transformer in the zoo exposes ``pipeline_layers()``: a list of modules
@@ -80,11 +81,11 @@ class SelfAttention(nn.Module):
         drop = self.dropout if self.training else 0.0
         if ops.attention_supported(qkv, self.head_dim, drop):
             # K8 HIP attention on the [B, S, heads, D] layout the projection produced: no
-            # transposes; it reads q/k/v and writes dQKV in place
+            # transposes; it reads q/k/v and writes dQKV in place (dropout: mask generated in-kernel)
             if self.rope is not None:
                 # K14: q and k rotated in one pass into a packed buffer (backward: in place on dQKV)
                 qkv = ops.rope_qkv(qkv.contiguous(), self.rope.cos, self.rope.sin, self.heads + self.kv_heads)
-            o = ops.attention_qkvpacked(qkv, self.heads, self.kv_heads, causal=self.causal)
+            o = ops.attention_qkvpacked(qkv, self.heads, self.kv_heads, causal=self.causal, dropout_p=drop)
             return linear(self.proj, o.view(b, s, self.heads * self.head_dim))
         q, k, v = qkv.split([self.heads, self.kv_heads, self.kv_heads], dim=2)
         q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)

@@ -11,8 +11,9 @@ kernels as madnn's zoo, not only on the fused optimizer and bucket kernels:
 * Hugging Face attention    -> the K8 MFMA flash-attention kernel, registered as
   the ``"madnn_k8"`` attention implementation (HF's ``AttentionInterface``):
   unmasked (or causal-only) bf16 attention with head dim 64/128 runs K8 straight
-  from HF's [B, H, S, D] views; padding masks, dropout, position biases and
-  decoding fall back to HF's SDPA path.
+  from HF's [B, H, S, D] views, attention dropout included (in-kernel mask);
+  padding masks, position biases and decoding fall back to HF's SDPA path, and so
+  does dropout with ``MADNN_ATTN_DROPOUT=0`` or under stream capture.
 
 Every swap keeps parameter and buffer names (state dicts interchange with the
 original model).  The reference had no kernels of its own at all.
@@ -72,11 +73,11 @@ def madnn_attention_forward(module, query, key, value, attention_mask, dropout: 
     """HF attention-interface entry: K8 for what it supports, HF SDPA for the rest."""
     is_causal = is_causal if is_causal is not None else getattr(module, "is_causal", True)
     q_len, kv_len = query.shape[2], key.shape[2]
-    if (attention_mask is None and position_bias is None and dropout == 0.0 and q_len == kv_len
+    if (attention_mask is None and position_bias is None and q_len == kv_len
             and not kwargs.get("output_attentions", False)
-            and ops.attention_supported(query, query.shape[-1]) and key.dtype == query.dtype):
+            and ops.attention_supported(query, query.shape[-1], dropout) and key.dtype == query.dtype):
         o = ops.attention(query.transpose(1, 2), key.transpose(1, 2), value.transpose(1, 2),
-                          causal=bool(is_causal and q_len > 1), scale=scaling)
+                          causal=bool(is_causal and q_len > 1), scale=scaling, dropout_p=dropout)
         _stats["k8"] += 1
         return o, None
     from transformers.integrations.sdpa_attention import sdpa_attention_forward

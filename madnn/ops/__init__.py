@@ -565,18 +565,19 @@ class _AttnFn(torch.autograd.Function):
     """q [B,S,H,D], k/v [B,S,Hkv,D] (strided views) -> o [B,S,H,D] contiguous."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale))
+    def forward(ctx, q, k, v, causal, scale, p=0.0, seed=0, offset=0):
+        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.causal, ctx.scale = causal, scale
+        ctx.drop = (p, seed, offset)   # the backward kernels regenerate the mask from these
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, float(ctx.scale))
-        return dq, dk, dv, None, None
+        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, float(ctx.scale), None, *ctx.drop)
+        return dq, dk, dv, None, None, None, None, None
 
 
 class _AttnPackedFn(torch.autograd.Function):
@@ -584,11 +585,12 @@ class _AttnPackedFn(torch.autograd.Function):
     into one buffer (no split/cat copies in either direction)."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, kv_heads, causal, scale):
+    def forward(ctx, qkv, heads, kv_heads, causal, scale, p=0.0, seed=0, offset=0):
         q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
-        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale))
+        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset)
         ctx.save_for_backward(qkv, o, lse)
         ctx.meta = (heads, kv_heads, bool(causal), float(scale))
+        ctx.drop = (p, seed, offset)
         # qkv is (a view of) a biased madnn Linear's output: the backward kernels also sum dQKV's
         # columns, which that Linear takes as its bias gradient (no column-sum pass of its own)
         ctx.colsum = ATTN_COLSUM and _from_biased_linear(qkv)
@@ -605,40 +607,70 @@ class _AttnPackedFn(torch.autograd.Function):
         cs = None
         if ctx.colsum:
             cs = torch.empty((heads + 2 * kv_heads) * qkv.size(-1), dtype=ctx.colsum_dtype, device=qkv.device)
-        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cs)
+        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cs, *ctx.drop)
         if cs is not None:
             _attach(dqkv, "_madnn_colsum", cs)
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 ATTN_COLSUM = os.environ.get("MADNN_ATTN_COLSUM", "1") != "0"  # A/B switch (see _AttnPackedFn.forward)
 
 
+ATTN_DROPOUT = os.environ.get("MADNN_ATTN_DROPOUT", "1") != "0"  # K8 with dropout > 0 (0: SDPA, as before)
+
+
 def attention_supported(t: torch.Tensor, head_dim: int, dropout: float = 0.0) -> bool:
-    """Inputs the K8 attention kernels take: bf16 HIP tensors, head dim 64/128, no dropout."""
-    return (t.device.type == "cuda" and t.dtype == torch.bfloat16 and head_dim in (64, 128)
-            and dropout == 0.0 and t.stride(-1) == 1)
+    """Inputs the K8 attention kernels take: bf16 HIP tensors, head dim 64/128, dropout in [0, 1).
+    With ``dropout > 0`` the kernels generate the mask themselves (Philox, regenerated in the
+    backward); that is refused -- callers fall back to SDPA -- when ``MADNN_ATTN_DROPOUT=0`` and while
+    a stream capture is in progress (the host-side draw of the generator offset cannot be captured)."""
+    if not (t.device.type == "cuda" and t.dtype == torch.bfloat16 and head_dim in (64, 128)
+            and 0.0 <= dropout < 1.0 and t.stride(-1) == 1):
+        return False
+    return dropout == 0.0 or (ATTN_DROPOUT and not torch.cuda.is_current_stream_capturing())
 
 
-def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None):
+def _attn_dropout_args(t: torch.Tensor, dropout_p: float, rng) -> tuple:
+    """``(p, seed, offset)`` of one K8 call, seed / offset as the signed 64-bit values the op schema
+    takes.  ``rng=None`` draws from torch's generator of the tensor's device and advances its offset,
+    so ``torch.manual_seed`` reproduces a run, ``torch.utils.checkpoint``'s RNG preservation replays
+    the same mask in the recompute, and checkpointed RNG streams cover it with no new state."""
+    if dropout_p == 0.0:
+        return 0.0, 0, 0
+    reference.attention_dropout_threshold(dropout_p)   # raises for a p that keeps nothing
+    if rng is None:
+        gen = torch.cuda.default_generators[t.device.index]
+        seed, offset = gen.initial_seed(), gen.get_offset()
+        gen.set_offset(offset + 4)
+    else:
+        seed, offset = rng
+    s64 = lambda x: ((int(x) + 2 ** 63) % 2 ** 64) - 2 ** 63
+    return float(dropout_p), s64(seed), s64(offset)
+
+
+def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dropout_p: float = 0.0, rng=None):
     """Scaled-dot-product attention on [B, S, heads, D] tensors (GQA when k/v have fewer heads).
-    Returns [B, S, H, D].  HIP bf16 inputs run K8; anything else runs SDPA."""
+    Returns [B, S, H, D].  HIP bf16 inputs run K8; anything else runs SDPA.  ``dropout_p`` drops
+    attention probabilities (K8: in-kernel mask, see :func:`reference.attention_dropout_mask`);
+    ``rng = (seed, offset)`` pins K8's mask, by default it is drawn from torch's device generator."""
     scale = scale if scale is not None else q.size(-1) ** -0.5
-    if attention_supported(q, q.size(-1)):
+    if attention_supported(q, q.size(-1), dropout_p):
         _need_native("attention")
-        return _AttnFn.apply(q, k, v, causal, scale)
-    return reference.attention(q, k, v, causal=causal, scale=scale)
+        return _AttnFn.apply(q, k, v, causal, scale, *_attn_dropout_args(q, dropout_p, rng))
+    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p)
 
 
-def attention_qkvpacked(qkv, heads: int, kv_heads: int, *, causal: bool = True, scale: Optional[float] = None):
-    """Attention straight from a packed projection ``qkv`` [B, S, heads + 2*kv_heads, D]."""
+def attention_qkvpacked(qkv, heads: int, kv_heads: int, *, causal: bool = True, scale: Optional[float] = None,
+                        dropout_p: float = 0.0, rng=None):
+    """Attention straight from a packed projection ``qkv`` [B, S, heads + 2*kv_heads, D]
+    (``dropout_p`` / ``rng`` as in :func:`attention`)."""
     d = qkv.size(-1)
     scale = scale if scale is not None else d ** -0.5
-    if attention_supported(qkv, d) and qkv.is_contiguous():
+    if attention_supported(qkv, d, dropout_p) and qkv.is_contiguous():
         _need_native("attention")
-        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale)
+        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_attn_dropout_args(qkv, dropout_p, rng))
     q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
-    return reference.attention(q, k, v, causal=causal, scale=scale)
+    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p)
 
 
 # ---------------------------------------------------------------- K14 / K15

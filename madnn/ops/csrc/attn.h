@@ -33,6 +33,13 @@ struct MadnnAttnArgs {
   // projection's bias gradient before the final reduce): [B * ceil(S / 128)][(H + 2 Hkv) * D] fp32,
   // dq in columns [0, H D), dk in [H D, (H + Hkv) D), dv in [(H + Hkv) D, (H + 2 Hkv) D)
   float* cpart;
+  // attention dropout (attn.hip header, "Dropout"): drop_threshold = round((1 - p) * 256) in 1..256,
+  // 0 = no dropout (today's kernels); drop_rp = 256 / drop_threshold, the rescale by the realised
+  // keep probability; the Philox key / counter base of this call
+  uint32_t drop_threshold;
+  float drop_rp;
+  uint64_t drop_seed;
+  uint64_t drop_offset;
 };
 
 }

@@ -27,6 +27,31 @@
 //    dispatched to one XCD work on the same heads, so K/V tiles hit in its L2.
 // Reference: the reference has no attention; this serves the
 // transformer configs of BASELINE.json (GPT-2 medium, BERT-large, Llama-3 8B).
+//
+// Dropout (the DROP instantiations of the three register-staged kernels; the LDS-DMA ring kernels
+// are not taken with dropout).  Keep / drop of one attention probability is a pure function of
+// (seed, offset, b, query head h, q, k, threshold) -- never of the tile shape, D, S, the kernel or the
+// lane -- so the forward, dQ (query on the lane) and dK/dV (key on the lane, looping over the query
+// heads of a KV group) kernels regenerate the same mask and no mask tensor exists in memory:
+//  * Philox4x32 with ten rounds (the full-strength count of Salmon et al. 2011; the quad sharing
+//    below already brings the cost to one call per 16 elements, so fewer rounds were not tried);
+//    key = (seed[31:0], seed[63:32] ^ offset[63:32]), counter = (offset[31:0], b*H + h, q >> 2, k >> 2);
+//  * the four 32-bit outputs are the 16 mask bytes of the 4 x 4 block (q >> 2, k >> 2): element
+//    (q, k) owns byte (k & 3) of word (q & 3) and is kept iff that byte < threshold, with
+//    threshold = floor((1 - p) * 256 + 0.5) in 1..256 (p is quantised to 1/256; a p that rounds to
+//    threshold 0 is rejected by the callers);
+//  * kept elements are scaled by rp = 256 / threshold, the reciprocal of the REALISED keep
+//    probability, so the expectation of the output is exact whatever the quantisation of p;
+//  * a lane holds 4 consecutive keys of one query (forward, dQ: one word of a block) or 4 consecutive
+//    queries of one key (dK/dV: one byte of each word), and the 4 lanes of a quad hold the 4 rows
+//    (columns) of the same blocks: each lane runs Philox for a quarter of the quad's blocks and the
+//    quad exchanges the words by DPP quad_perm broadcasts;
+//  * forward: l and the LSE are those of the undropped softmax, the mask is applied to p before
+//    pack_acc, rp is folded into the final 1 / l; backward: dS = P (rp M dPraw - delta) with delta =
+//    rowsum(dO * O) unchanged (O contains the dropout), dV += (rp M P)^T dO; the dP accumulators
+//    start at zero (the -delta start of ACCD would be masked along with dPraw).
+// madnn.ops.reference.attention_dropout_mask is the host mirror (bit-identical);
+// attn_dropout_mask_kernel writes the mask out through the same drop_block() for tests.
 #include <type_traits>
 
 #include "attn.h"
@@ -198,6 +223,79 @@ __device__ __forceinline__ void store4_bf16(uint16_t* p, float a, float b, float
   *reinterpret_cast<u32x2*>(p) = u32x2{lo, hi};
 }
 
+// ------------------------------------------------------------------ dropout mask
+constexpr int kPhiloxRounds = 10;
+
+struct DropRng {
+  uint32_t k0, k1, c0;  // Philox key, counter word 0
+};
+
+__device__ __forceinline__ DropRng drop_rng(uint64_t seed, uint64_t offset) {
+  return DropRng{(uint32_t)seed, (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32), (uint32_t)offset};
+}
+
+// The 16 mask bytes of head bh's 4 x 4 block (queries 4 qb..4 qb + 3) x (keys 4 kb..4 kb + 3):
+// Philox4x32 on the counter (c0, bh, qb, kb); word = query & 3, byte = key & 3.
+__device__ __forceinline__ u32x4 drop_block(const DropRng& g, uint32_t bh, uint32_t qb, uint32_t kb) {
+  uint32_t c0 = g.c0, c1 = bh, c2 = qb, c3 = kb, k0 = g.k0, k1 = g.k1;
+#pragma unroll
+  for (int r = 0; r < kPhiloxRounds; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return u32x4{c0, c1, c2, c3};
+}
+
+__device__ __forceinline__ uint32_t drop_byte(uint32_t word, int i) { return (word >> (8 * i)) & 0xffu; }
+
+// v of lane j of this lane's quad (DPP quad_perm [j, j, j, j]); j a constant after unrolling
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v, int j) {
+  switch (j) {
+    case 0: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x00, 0xf, 0xf, true);
+    case 1: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x55, 0xf, 0xf, true);
+    case 2: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xaa, 0xf, 0xf, true);
+    default: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xff, 0xf, 0xf, true);
+  }
+}
+
+// Query on the lane: f(r, byte) for the 16 accumulator registers of one 32-key half (keys kbase +
+// acc_row(r, hh), kbase a multiple of 32) of query qrow.  Registers 4g..4g+3 are the 4 keys of block
+// (qrow >> 2, (kbase + 8g + 4hh) >> 2); quad lane j computes block g = j, every lane takes its word
+// (qrow & 3 == lane & 3: the workgroup's first row is a multiple of 32).  All 64 lanes must be active.
+template <class F>
+__device__ __forceinline__ void drop_bytes_q(const DropRng& g, uint32_t bh, int qrow, int kbase, int hh, int lane, F&& f) {
+  const int j = lane & 3;
+  const u32x4 w = drop_block(g, bh, (uint32_t)qrow >> 2, (uint32_t)(kbase + 8 * j + 4 * hh) >> 2);
+#pragma unroll
+  for (int gi = 0; gi < 4; ++gi) {
+    const uint32_t x0 = quad_bcast(w[0], gi), x1 = quad_bcast(w[1], gi), x2 = quad_bcast(w[2], gi),
+                   x3 = quad_bcast(w[3], gi);
+    const uint32_t word = j == 0 ? x0 : j == 1 ? x1 : j == 2 ? x2 : x3;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f(4 * gi + i, drop_byte(word, i));
+  }
+}
+
+// Key on the lane: f(r, byte) for the 16 registers of one 32-query half (queries qbase + acc_row(r,
+// hh), qbase a multiple of 32) of key krow.  Registers 4g..4g+3 are the 4 queries of block ((qbase +
+// 8g + 4hh) >> 2, krow >> 2): byte (krow & 3 == lane & 3) of each of its words.
+template <class F>
+__device__ __forceinline__ void drop_bytes_k(const DropRng& g, uint32_t bh, int krow, int qbase, int hh, int lane, F&& f) {
+  const int j = lane & 3;
+  const u32x4 w = drop_block(g, bh, (uint32_t)(qbase + 8 * j + 4 * hh) >> 2, (uint32_t)krow >> 2);
+#pragma unroll
+  for (int gi = 0; gi < 4; ++gi) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f(4 * gi + i, drop_byte(quad_bcast(w[i], gi), j));
+  }
+}
+
 // ------------------------------------------------------------------ forward
 // The causal / sequence-end mask is one compare of a compile-time key offset against a per-lane
 // limit, and the running max is moved only when a row's max grows by more than 2^8 (lazy rescale:
@@ -255,7 +353,7 @@ __device__ __forceinline__ void softmax_tile(f32x16 (&sc)[2], f32x16 (&o)[DB], f
 
 // D = 128 is built for 2 waves per SIMD (256 VGPRs, a few spills; 348 and one wave unbounded):
 // +27 % at Llama-3 8B's shape, profiles/r5_attn_ab_occupancy.json
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(const MadnnAttnArgs a) {
   constexpr int DS = D / 16, DB = D / 32;
   __shared__ __attribute__((aligned(16))) uint16_t sK[2][kTile * D];
@@ -318,6 +416,15 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
         }
       }
       softmax_tile<DB>(sc, o, m, mi, l, mref);
+      if constexpr (DROP) {  // l has the undropped row sum; O takes M . P (rp is folded into inv)
+        const DropRng rng = drop_rng(a.drop_seed, a.drop_offset);
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+          drop_bytes_q(rng, b * a.H + h, qrow, k0 + kb * 32, hh, lane, [&](int r, uint32_t byte) {
+            sc[kb][r] = byte < a.drop_threshold ? sc[kb][r] : 0.f;
+          });
+        }
+      }
       // O^T[d][q] += sum_key V[key][d] P^T[key][q]
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -336,7 +443,8 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
     __syncthreads();
   }
   const float lt = l + __shfl_xor(l, 32);
-  const float inv = lt > 0.f ? 1.f / lt : 0.f;
+  float inv = lt > 0.f ? 1.f / lt : 0.f;
+  if constexpr (DROP) inv *= a.drop_rp;
   if (qrow < a.S) {
     uint16_t* op = a.o + b * a.o_sb + h * a.o_sh + (int64_t)qrow * a.o_ss;
 #pragma unroll
@@ -361,10 +469,12 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
 // other (one half's S / dP accumulators live) and the LSE is a per-element subtraction: 256 VGPRs
 // (380 and one wave before), backward +11 % at Llama-3 8B's shape (profiles/r5_attn_ab_occupancy.json;
 // at D = 64 the 2-wave build measured neutral).
-template <int D, bool CAUSAL>
+// DROP: dS = P (rp M dPraw - delta): the mask and rp go onto the raw dP before the subtraction, so the
+// dP accumulators start at zero at D = 64 too (no ACCD).
+template <int D, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel(const MadnnAttnArgs a) {
   constexpr int DS = D / 16, DB = D / 32;
-  constexpr bool ACCD = D == 64, KSPLIT = D == 128;
+  constexpr bool ACCD = D == 64 && !DROP, KSPLIT = D == 128;
   // K and V stages in one block: after the loop the column-sum epilogue reuses all of it as a
   // [128 rows][D] fp32 image (4 * 64 * D bf16 = 128 * D fp32)
   __shared__ __attribute__((aligned(16))) uint16_t sKV[4][kTile * D];
@@ -442,6 +552,10 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
 #pragma unroll
           for (int r = 0; r < 16; ++r) sc[r] = (kb * 32 + acc_row(r, 0) <= lim) ? sc[r] : __builtin_inff();
         }
+        if constexpr (DROP) {
+          drop_bytes_q(drop_rng(a.drop_seed, a.drop_offset), b * a.H + h, qrow, k0 + kb * 32, hh, lane,
+                       [&](int r, uint32_t byte) { dp[r] = byte < a.drop_threshold ? dp[r] * a.drop_rp : 0.f; });
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) sc[r] = ex2(-sc[r] - lse) * (dp[r] - dl);
 #pragma unroll
@@ -473,6 +587,15 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) sc[kb][r] = (kb * 32 + acc_row(r, 0) <= lim) ? sc[kb][r] : __builtin_inff();
+        }
+      }
+      if constexpr (DROP) {
+        const DropRng rng = drop_rng(a.drop_seed, a.drop_offset);
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+          drop_bytes_q(rng, b * a.H + h, qrow, k0 + kb * 32, hh, lane, [&](int r, uint32_t byte) {
+            dp[kb][r] = byte < a.drop_threshold ? dp[kb][r] * a.drop_rp : 0.f;
+          });
         }
       }
 #pragma unroll
@@ -925,10 +1048,14 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_dma_kernel(const MadnnAttnA
 // r4_ab_attn_valu_trees.log).  The LSE stays a per-element subtraction here: started in the S
 // accumulators as in the DMA kernel, the extra LDS reads made hipcc wait on the next tile's staging
 // loads inside the MFMA chain (backward +40 %).  Two tiles per trip (compile-time LDS buffer index).
-template <int D, bool CAUSAL>
-__global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_kernel(const MadnnAttnArgs a) {
+// DROP: the mask is that of the QUERY head of the tile (not of the KV head); dV takes rp M P, dK the
+// same dS = P (rp M dPraw - delta) as dQ (no ACCD).  At D = 64 it is bounded to 2 waves per SIMD (256 VGPRs,
+// no spill; 264 and one wave unbounded): forward + backward -16 % / -13 % at the GPT-2 medium / BERT-large
+// shapes (docs/PERF.md, round 11).
+template <int D, bool CAUSAL, bool DROP = false>
+__global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dkdv_kernel(const MadnnAttnArgs a) {
   constexpr int DS = D / 16, DB = D / 32;
-  constexpr bool ACCD = D == 64;
+  constexpr bool ACCD = D == 64 && !DROP;
   __shared__ __attribute__((aligned(16))) uint16_t sQ[2][kTile * D];
   __shared__ __attribute__((aligned(16))) uint16_t sO[2][kTile * D];  // dO
   __shared__ float sL[2][kTile], sD[2][kTile];
@@ -1006,6 +1133,7 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_kernel(const MadnnAttn
   }
   __syncthreads();
   int cur_t = 0, nxt_h = 0, nxt_t = 0;  // this tile's query-tile index; the next tile's (head, tile)
+  int cur_h = 0;                        // this tile's query head within the group (DROP)
   // two tiles per trip with the LDS buffer index a compile-time constant, so the buffer base folds
   // into the ds_read immediate offsets instead of costing a VALU op per read address
   int it = 0;
@@ -1027,6 +1155,8 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_kernel(const MadnnAttn
     }
     const int q0 = (t0 + cur_t) * kTile;
     cur_t = nxt_t;
+    const int hq = hk * G + cur_h;
+    cur_h = nxt_h;
     if (!CAUSAL || q0 + kTile - 1 >= k0w) {
       f32x16 sc[2], dp[2];
 #pragma unroll
@@ -1052,14 +1182,28 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_kernel(const MadnnAttn
           for (int r = 0; r < 16; ++r) sc[qb][r] = (qb * 32 + acc_row(r, 0) >= lo) ? sc[qb][r] : -__builtin_inff();
         }
       }
+      if constexpr (DROP) {
+        const DropRng rng = drop_rng(a.drop_seed, a.drop_offset);
 #pragma unroll
-      for (int qb = 0; qb < 2; ++qb) {
+        for (int qb = 0; qb < 2; ++qb) {
+          drop_bytes_k(rng, b * a.H + hq, krow, q0 + qb * 32, hh, lane, [&](int r, uint32_t byte) {
+            const int qi = qb * 32 + acc_row(r, hh);
+            const float p = ex2(fmaf(sc[qb][r], a.scale_log2, -sL[cur][qi]));
+            const float pd = byte < a.drop_threshold ? p * a.drop_rp : 0.f;  // rp M P
+            sc[qb][r] = pd;
+            dp[qb][r] = fmaf(pd, dp[qb][r], -p * sD[cur][qi]);  // P (rp M dPraw - delta)
+          });
+        }
+      } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int qi = qb * 32 + acc_row(r, hh);
-          const float p = ex2(fmaf(sc[qb][r], a.scale_log2, -sL[cur][qi]));
-          sc[qb][r] = p;
-          dp[qb][r] = ACCD ? p * dp[qb][r] : p * (dp[qb][r] - sD[cur][qi]);
+        for (int qb = 0; qb < 2; ++qb) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int qi = qb * 32 + acc_row(r, hh);
+            const float p = ex2(fmaf(sc[qb][r], a.scale_log2, -sL[cur][qi]));
+            sc[qb][r] = p;
+            dp[qb][r] = ACCD ? p * dp[qb][r] : p * (dp[qb][r] - sD[cur][qi]);
+          }
         }
       }
       // dV[key][d] += sum_q P[q][key] dO[q][d];  dK[key][d] += sum_q dS[q][key] Q[q][d]
@@ -1154,6 +1298,19 @@ __global__ __launch_bounds__(1024) void attn_colsum_finalize_kernel(const float*
   }
 }
 
+// The dropout mask itself (tests / debugging): out[b][h][q][k] = 1 iff the element is kept
+__global__ __launch_bounds__(256) void attn_dropout_mask_kernel(uint8_t* __restrict__ out, int S, int64_t n, uint32_t threshold,
+                                                                uint64_t seed, uint64_t offset) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  const int k = (int)(idx % S), q = (int)((idx / S) % S);
+  const uint32_t bh = (uint32_t)(idx / ((int64_t)S * S));
+  const u32x4 w = drop_block(drop_rng(seed, offset), bh, (uint32_t)q >> 2, (uint32_t)k >> 2);
+  const int qi = q & 3;
+  const uint32_t word = qi == 0 ? w[0] : qi == 1 ? w[1] : qi == 2 ? w[2] : w[3];
+  out[idx] = drop_byte(word, k & 3) < threshold ? 1 : 0;
+}
+
 // madnn_attn_tune keys (A/B and the tests of the register-staged fallbacks, which serve sequence
 // lengths that are not multiples of 64 and D = 128): 7 = D = 64 dK/dV on the 3-stage LDS-DMA ring,
 // 8 = D = 64 forward on the K / V LDS-DMA ring (0: the register-staged kernels)
@@ -1163,7 +1320,9 @@ int g_attn_fwd_dma = 1;
 template <int D, bool CAUSAL>
 hipError_t launch_fwd(const MadnnAttnArgs& a, hipStream_t st) {
   const int nqb = (a.S + kRowsWG - 1) / kRowsWG;
-  if (D == 64 && g_attn_fwd_dma && a.S % kTile == 0) {
+  if (a.drop_threshold != 0) {  // dropout: the register-staged kernel at every shape
+    hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, true>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
+  } else if (D == 64 && g_attn_fwd_dma && a.S % kTile == 0) {
     hipLaunchKernelGGL((attn_fwd_dma_kernel<CAUSAL>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
   } else {
     hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
@@ -1174,6 +1333,12 @@ hipError_t launch_fwd(const MadnnAttnArgs& a, hipStream_t st) {
 template <int D, bool CAUSAL>
 hipError_t launch_bwd(const MadnnAttnArgs& a, hipStream_t st) {
   const int nb = (a.S + kRowsWG - 1) / kRowsWG;
+  if (a.drop_threshold != 0) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CAUSAL, true>), dim3(nb * a.B * a.H), dim3(kThreads), 0, st, a);
+    MADNN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, true>), dim3(nb * a.B * a.Hkv), dim3(kThreads), 0, st, a);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CAUSAL>), dim3(nb * a.B * a.H), dim3(kThreads), 0, st, a);
   MADNN_HIP_CHECK(hipGetLastError());
   if (D == 64 && g_attn_dkdv_dma && a.S % kTile == 0) {
@@ -1217,6 +1382,23 @@ hipError_t madnn_attn_colsum_finalize(const float* cpart, int64_t R, int64_t C, 
   if (R <= 0 || C <= 0) return hipSuccess;
   hipLaunchKernelGGL(attn_colsum_finalize_kernel, dim3((unsigned)((C + 31) / 32)), dim3(1024), 0, st, cpart, (int)R,
                      (int)C, out, out_bf16);
+  return hipGetLastError();
+}
+
+// threshold = floor((1 - p) * 256 + 0.5): 1..256 for a usable p, 0 when p quantises to keep-nothing,
+// -1 for p outside [0, 1)
+int madnn_attn_dropout_threshold(double p) {
+  if (!(p >= 0.0 && p < 1.0)) return -1;
+  return (int)((1.0 - p) * 256.0 + 0.5);
+}
+
+hipError_t madnn_attn_dropout_mask(uint8_t* out, int B, int H, int S, uint32_t threshold, uint64_t seed, uint64_t offset,
+                                   hipStream_t st) {
+  const int64_t n = (int64_t)B * H * S * S;
+  if (n <= 0) return hipSuccess;
+  if ((n + 255) / 256 > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, S, n, threshold,
+                     seed, offset);
   return hipGetLastError();
 }
 

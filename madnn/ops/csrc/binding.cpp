@@ -48,6 +48,8 @@ hipError_t madnn_attn_fwd(const MadnnAttnArgs*, int, int, hipStream_t);
 hipError_t madnn_attn_bwd(const MadnnAttnArgs*, int, int, hipStream_t);
 int64_t madnn_attn_colsum_rows(int, int);
 hipError_t madnn_attn_colsum_finalize(const float*, int64_t, int64_t, void*, int, hipStream_t);
+int madnn_attn_dropout_threshold(double);
+hipError_t madnn_attn_dropout_mask(uint8_t*, int, int, int, uint32_t, uint64_t, uint64_t, hipStream_t);
 int madnn_maxpool_supported(int64_t, int, int);
 hipError_t madnn_maxpool_fwd(const void*, void*, void*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 int madnn_pool_bn_supported(int64_t, int);
@@ -1521,9 +1523,26 @@ MadnnAttnArgs attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tens
   return a;
 }
 
+// Dropout probability -> the mask threshold (attn.hip "Dropout"); p == 0 is "no dropout".
+uint32_t attn_drop_threshold(double p) {
+  const int t = madnn_attn_dropout_threshold(p);
+  TORCH_CHECK(t >= 0, "attention: dropout p must be in [0, 1), got ", p);
+  TORCH_CHECK(t >= 1, "attention: dropout p = ", p, " keeps nothing at the mask's 1/256 resolution");
+  return (uint32_t)t;
+}
+
+void attn_set_dropout(MadnnAttnArgs& a, double p, int64_t seed, int64_t offset) {
+  if (p == 0.0) return;  // drop_threshold = 0: the kernels without dropout
+  a.drop_threshold = attn_drop_threshold(p);
+  a.drop_rp = 256.f / (float)a.drop_threshold;
+  a.drop_seed = (uint64_t)seed;
+  a.drop_offset = (uint64_t)offset;
+}
+
 std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                                            bool causal, double scale) {
+                                            bool causal, double scale, double p, int64_t seed, int64_t offset) {
   MadnnAttnArgs a = attn_args(q, k, v, scale);
+  attn_set_dropout(a, p, seed, offset);
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor o = at::empty({q.size(0), q.size(1), q.size(2), q.size(3)}, q.options());
   at::Tensor lse = at::empty({q.size(0), q.size(2), q.size(1)}, q.options().dtype(at::kFloat));
@@ -1537,8 +1556,10 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tenso
 // Writes dq/dk/dv into the given (possibly strided, e.g. one packed dQKV buffer) outputs.
 void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
               const at::Tensor& o, const at::Tensor& lse, const at::Tensor& dq, const at::Tensor& dk,
-              const at::Tensor& dv, bool causal, double scale, const c10::optional<at::Tensor>& colsum) {
+              const at::Tensor& dv, bool causal, double scale, const c10::optional<at::Tensor>& colsum, double p,
+              int64_t seed, int64_t offset) {
   MadnnAttnArgs a = attn_args(q, k, v, scale);
+  attn_set_dropout(a, p, seed, offset);
   const int64_t D = q.size(3);
   TORCH_CHECK(o.is_contiguous() && o.sizes() == q.sizes(), "attn_bwd: o must be contiguous [B, S, H, D]");
   at::Tensor doc = dout.contiguous();
@@ -1579,6 +1600,18 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
     check(madnn_attn_colsum_finalize(a.cpart, R, C, colsum->data_ptr(), colsum->scalar_type() == at::kBFloat16 ? 1 : 0,
                                      cur_stream(q)),
           "attn_colsum");
+}
+
+// The K8 dropout mask as a tensor: uint8 [B, H, S, S], 1 = kept (tests / debugging; the attention
+// kernels regenerate it in registers), on the current device.
+at::Tensor attn_dropout_mask(int64_t B, int64_t H, int64_t S, double p, int64_t seed, int64_t offset) {
+  TORCH_CHECK(B >= 0 && H >= 0 && S >= 0 && B * H < (1ll << 31) && S < (1ll << 30), "attn_dropout_mask: shape");
+  const uint32_t thr = attn_drop_threshold(p);
+  at::Tensor out = at::empty({B, H, S, S}, at::TensorOptions().device(at::kCUDA).dtype(at::kByte));
+  check(madnn_attn_dropout_mask(out.data_ptr<uint8_t>(), (int)B, (int)H, (int)S, thr, (uint64_t)seed, (uint64_t)offset,
+                                cur_stream(out)),
+        "attn_dropout_mask");
+  return out;
 }
 
 // Hardware-queue aliasing probe (probe.hip): bounded flag wait / flag set on the current stream.
@@ -1655,10 +1688,13 @@ TORCH_LIBRARY(madnn, m) {
   m.def(
       "bn_bwd_dual(Tensor dy, Tensor x, Tensor r, Tensor mask, Tensor? w, Tensor save_mean, Tensor save_invstd, "
       "Tensor? w_r, Tensor save_mean_r, Tensor save_invstd_r) -> Tensor[]");
-  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale) -> (Tensor, Tensor)");
+  m.def(
+      "attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, float p=0.0, int seed=0, int offset=0) -> "
+      "(Tensor, Tensor)");
   m.def(
       "attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, "
-      "Tensor(c!) dv, bool causal, float scale, Tensor(d!)? colsum=None) -> ()");
+      "Tensor(c!) dv, bool causal, float scale, Tensor(d!)? colsum=None, float p=0.0, int seed=0, int offset=0) -> ()");
+  m.def("attn_dropout_mask(int B, int H, int S, float p, int seed, int offset) -> Tensor", &attn_dropout_mask);
   m.def("conv1x1_fwd(Tensor x, Tensor w, bool stats) -> (Tensor, Tensor)");
   m.def("conv1x1_dgrad(Tensor dy, Tensor w, Tensor? res=None, Tensor? resmask=None) -> Tensor");
   m.def("conv1x1_dgrad_bnb(Tensor dy, Tensor w, Tensor bny, Tensor scale, Tensor shift) -> (Tensor, Tensor)");

@@ -143,11 +143,57 @@ def cross_entropy(logits, targets, *, shift=False, vocab=None, ignore_index=-100
     return F.cross_entropy(logits[..., :v].reshape(-1, v).float(), targets.reshape(-1), ignore_index=ignore_index)
 
 
-def attention(q, k, v, *, causal=True, scale=None):
-    """[B, S, H, D] / [B, S, Hkv, D] -> [B, S, H, D] via SDPA (fp32 oracle when given fp32)."""
+def attention(q, k, v, *, causal=True, scale=None, dropout_p=0.0):
+    """[B, S, H, D] / [B, S, Hkv, D] -> [B, S, H, D] via SDPA (fp32 oracle when given fp32).
+    ``dropout_p`` is SDPA's own dropout (torch's mask, not K8's)."""
     import torch.nn.functional as F
 
     h, hkv = q.size(2), k.size(2)
-    o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
+    o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), dropout_p=dropout_p,
                                        is_causal=causal, scale=scale, enable_gqa=h != hkv)
     return o.transpose(1, 2).contiguous()
+
+
+DROPOUT_BITS = 8  # K8's dropout mask: one byte per attention probability
+
+
+def attention_dropout_threshold(p: float) -> int:
+    """K8 keeps an element iff its mask byte is below ``floor((1 - p) * 256 + 0.5)`` (p quantised to
+    1/256; the kept ones are scaled by ``256 / threshold``).  Raises for p outside [0, 1) and for a p
+    that quantises to keep-nothing."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attention dropout p must be in [0, 1), got {p}")
+    thr = int(math.floor((1.0 - float(p)) * 256.0 + 0.5))
+    if thr < 1:
+        raise ValueError(f"attention dropout p = {p} keeps nothing at the mask's 1/256 resolution")
+    return thr
+
+
+def attention_dropout_mask(B: int, H: int, S: int, p: float, seed: int, offset: int) -> torch.Tensor:
+    """The keep mask of K8's attention dropout, bool [B, H, S, S] (h = query head), on the CPU in
+    integer arithmetic: bit-identical to the device function ``drop_block`` of ``csrc/attn.hip``.
+    Philox4x32-10, key (seed lo, seed hi ^ offset hi), counter (offset lo, b*H + h, q >> 2, k >> 2);
+    the four output words are the 16 bytes of the 4 x 4 block: element (q, k) owns byte ``k & 3`` of
+    word ``q & 3`` and is kept iff it is ``< threshold``."""
+    import numpy as np
+
+    thr = attention_dropout_threshold(p)
+    seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    m32 = np.uint64(0xFFFFFFFF)
+    nb = (S + 3) // 4
+    shape = (B * H, nb, nb)
+    c0 = np.full(shape, offset & 0xFFFFFFFF, dtype=np.uint64)
+    c1 = np.broadcast_to(np.arange(B * H, dtype=np.uint64)[:, None, None], shape).copy()
+    c2 = np.broadcast_to(np.arange(nb, dtype=np.uint64)[None, :, None], shape).copy()
+    c3 = np.broadcast_to(np.arange(nb, dtype=np.uint64)[None, None, :], shape).copy()
+    k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) ^ (offset >> 32)) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2   # 32 x 32 -> 64 bit, exact
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & m32,
+                          (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & m32)
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    words = np.stack([c0, c1, c2, c3], axis=2)                              # [BH, qb, q & 3, kb]
+    shifts = (np.arange(4, dtype=np.uint64) * np.uint64(8))
+    byts = (words[..., None] >> shifts) & np.uint64(0xFF)                   # [BH, qb, q & 3, kb, k & 3]
+    keep = (byts < np.uint64(thr)).reshape(B, H, 4 * nb, 4 * nb)[:, :, :S, :S]
+    return torch.from_numpy(np.ascontiguousarray(keep))
