@@ -790,12 +790,34 @@ def conv1x1_route(cin: int, cout: int) -> tuple:
 
 _K9_WGRAD = os.environ.get("MADNN_K9_WGRAD", "miopen")  # "k9" | "miopen" (A/B runs)
 _K9_DGRAD = os.environ.get("MADNN_K9_DGRAD", "narrow")  # "wide" | "narrow" (A/B runs)
+# A/B switch: K9's forward / data-grad main loop.  Off: register-staged; on: the LDS-DMA ring (weight slice
+# LDS-resident) on the shapes whose slice fits its 32 KiB (conv.hip use_ring); the others stay register-staged.
+K9_RING = os.environ.get("MADNN_K9_RING", "1") != "0"
+_K9_TUNE = []
+
+
+def conv1x1_tune(key: int, value: int = -1) -> int:
+    """K9's native tunables (``madnn_conv1x1_tune``): key 0 the forward / data-grad persistent grid target,
+    1 the weight-grad workgroups, 2 the XCD remap, 3 the ring switch.  Sets ``value`` (>= 0) and returns the
+    previous one; ``value < 0`` only reads."""
+    _need_native("conv1x1_tune")
+    if not _K9_TUNE:
+        import ctypes
+
+        _K9_TUNE.append(ctypes.CDLL(str(_KERNELS)).madnn_conv1x1_tune)
+    return int(_K9_TUNE[0](int(key), int(value)))
+
+
+def _k9():
+    """``torch.ops.madnn`` for a K9 forward / data-grad launch, the native ring switch set to ``K9_RING``."""
+    conv1x1_tune(3, 1 if K9_RING else 0)
+    return torch.ops.madnn
 
 
 def _routed_conv1x1_fwd(fwd: str, x: torch.Tensor, w: torch.Tensor, stats: bool):
     """``(y, part)`` on K9 or the library (then an empty ``part``), as :func:`conv1x1_route` chose."""
     if fwd == "k9":
-        return torch.ops.madnn.conv1x1_fwd(x, w, bool(stats))
+        return _k9().conv1x1_fwd(x, w, bool(stats))
     y = F.conv2d(x, w) if x.dim() == 4 else torch.mm(x, w.reshape(w.size(0), -1).t())
     return y, x.new_empty((0, 2, w.size(0)), dtype=torch.float32)
 
@@ -852,7 +874,7 @@ class _Conv1x1Fn(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             if dgrad == "k9":
-                dx = torch.ops.madnn.conv1x1_dgrad(dy, w, res, resmask)
+                dx = _k9().conv1x1_dgrad(dy, w, res, resmask)
             else:
                 w2 = w.reshape(w.size(0), -1)
                 if res is not None:
@@ -922,7 +944,7 @@ class _BNReluConv1x1EpiFn(torch.autograd.Function):
     def backward(ctx, dout, _dpart):
         y, a, w, bn_w, mean, invstd, scale, shift = ctx.saved_tensors
         dout = _nhwc(dout.to(y.dtype))
-        da, part = torch.ops.madnn.conv1x1_dgrad_bnb(dout, w, y, scale, shift)
+        da, part = _k9().conv1x1_dgrad_bnb(dout, w, y, scale, shift)
         dw = _routed_conv1x1_wgrad(ctx.wgrad, dout, a, w)
         dy, dbw, dbb = torch.ops.madnn.bn_bwd_ext(da, y, bn_w, mean, invstd, scale, shift, part, True)
         need_bn = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
@@ -959,7 +981,7 @@ def bn_relu_conv1x1_epi_supported(y: torch.Tensor, bn, w: torch.Tensor) -> bool:
 def _k9f_head(y2, w3, bn2_w, bn2_b, bn2, stats_in):
     """Both K9F nodes' forward up to conv3 -> (a2, y3, y3's statistics, bn2's (mean, invstd, scale, shift))."""
     a2, mean2, invstd2, scale2, shift2, _ = _bn_fwd_train(y2, None, bn2_w, bn2_b, bn2, True, stats_in)
-    y3, part = torch.ops.madnn.conv1x1_fwd(a2, w3, True)
+    y3, part = _k9().conv1x1_fwd(a2, w3, True)
     return a2, y3, part, (mean2, invstd2, scale2, shift2)
 
 
@@ -1042,7 +1064,7 @@ class _BN2Conv3BN3DualFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y2, w3, bn2_w, bn2_b, bn3_w, bn3_b, xf, w_ds, bnd_w, bnd_b, bn2, bn3, bn_ds, stats_in):
         a2, y3, part, bn2_stats = _k9f_head(y2, w3, bn2_w, bn2_b, bn2, stats_in)
-        yd, part_d = torch.ops.madnn.conv1x1_fwd(xf, w_ds, True)
+        yd, part_d = _k9().conv1x1_fwd(xf, w_ds, True)
         out, mask, mean3, invstd3, _, _, mean_d, invstd_d, _, _ = torch.ops.madnn.bn_fwd_dual(
             y3, yd, bn3_w, bn3_b, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked, float(bn3.momentum),
             float(bn3.eps), part, bnd_w, bnd_b, bn_ds.running_mean, bn_ds.running_var, bn_ds.num_batches_tracked,
@@ -2098,7 +2120,7 @@ __all__ = [
     "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
     "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
     "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",
-    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "stem_conv", "stem_supported", "stem_bn_relu_maxpool", "stem_bn_relu_maxpool_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
+    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "conv1x1_tune", "stem_conv", "stem_supported", "stem_bn_relu_maxpool", "stem_bn_relu_maxpool_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
 ]

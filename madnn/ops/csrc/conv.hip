@@ -30,6 +30,9 @@
 // during this step's MFMAs; 64 KiB of LDS and <= 256 VGPRs: 2 workgroups (8 waves) per
 // CU.  Forward / dgrad workgroups are persistent: a workgroup keeps its i tile and walks
 // its j tiles, so loading tile t+1 overlaps tile t's MFMAs and epilogue.
+// Where the workgroup's weight slice fits 32 KiB, forward and data grad run ring_kernel instead: the slice stays
+// in LDS for the whole walk and the activation rows arrive by LDS-DMA through a 3-stage ring (below; the
+// register-staged gemm_kernel remains for the other shapes, the weight grad and as MADNN_K9_RING=0).
 //
 // Fused BatchNorm statistics (forward): the workgroup accumulates, per output channel,
 // the sum and sum of squares of the bf16-rounded outputs it stores, in registers across
@@ -39,6 +42,8 @@
 // (A BatchNorm apply + ReLU prologue on the X operand, a BN-reduction epilogue over a residual
 // ReLU's bit mask and a stride-2 residual epilogue were measured, lost their A/Bs and were removed
 // in round 6: docs/PERF.md.)
+#include <cstdlib>
+
 #include "mfma.h"
 
 namespace madnn {
@@ -55,6 +60,11 @@ struct Tune {
   int fwd_wg = kTargetWG;  // forward / dgrad persistent grid target
   int wgrad_wg = 2 * kNumCU;  // weight-grad workgroups (tiles x m splits)
   int xcd = 1;             // XCD-aware workgroup remap
+  int ring = ring_default();  // store-mode main loop: 0 register-staged, 1 LDS-DMA ring where it applies (use_ring)
+  static int ring_default() {
+    const char* e = getenv("MADNN_K9_RING");
+    return e != nullptr && *e != 0 ? atoi(e) : 1;
+  }
 };
 inline Tune& tune() {
   static Tune t;
@@ -362,6 +372,335 @@ template <bool A_COL, bool B_COL, int BI, int BJ, int MODE, bool STATS, bool BNB
 hipError_t launch(const GemmArgs& p, int grid, hipStream_t s) {
   hipLaunchKernelGGL((gemm_kernel<A_COL, B_COL, BI, BJ, MODE, STATS, BNB>), dim3(grid), dim3(kThreads), 0, s, p);
   return hipGetLastError();
+}
+
+// ---- K9 ring: the store-mode main loop with LDS-DMA operands (docs/ARCHITECTURE.md "K9 ring schedule") ----
+// The workgroup's weight slice A [BI][K] is loaded once and stays in LDS for the whole persistent walk (the
+// register-staged loop loads it again in every k step of every tile); the B operand (activation rows) streams
+// through a ring of kRingStages 64-deep stages, written by global_load_lds_dwordx4 straight into the swz<64>
+// row image Stage::frag reads.  While step u's MFMAs issue, steps u+1 and u+2 are in flight, across tile
+// boundaries and through the epilogue; waits are counted vmcnt(N) (wait_vm below), never a drain inside a walk.
+// Same MFMA instruction, same ascending k, same epilogue arithmetic and thread map as gemm_kernel: bitwise the
+// same outputs and partial rows.
+constexpr int kRingStages = 3;
+constexpr int kBStage = 128 * kBK;  // bf16 elements of one B stage: [128 j][64 k], 16 KiB
+
+// LDS-DMA from a wave-uniform base plus a 32-bit per-lane byte offset (no 64-bit per-lane address); M0 is set
+// and restored inside the statement (common.h glds16), and the leading s_nop covers a base that was formed
+// with v_readfirstlane
+__device__ __forceinline__ void glds16_off(const void* base, unsigned voff, unsigned lds_byte) {
+  const unsigned lds = __builtin_amdgcn_readfirstlane(lds_byte);
+  unsigned keep;
+  asm volatile(
+      "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(base), "s"(lds)
+      : "memory");
+}
+
+// LDS accesses retired, then the barrier (a raw s_barrier: __syncthreads' fences would drain vmcnt)
+__device__ __forceinline__ void ring_bar() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int N>
+__device__ __forceinline__ void vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// Wait until this wave's DMA of step u has landed.  VMEM operations retire in issue order on one counter; the
+// operations a wave has issued after step u's 4 DMA instructions are, in order: the epilogue of step u-2 (if
+// it ended a tile), the 4 DMA instructions of step u+1 (if the stream has one: `next`), the epilogue of step
+// u-1 (if it ended a tile).  An epilogue followed by another step belongs to a full tile (the partial tile is
+// the last of the walk), so it has issued exactly EST global stores per wave, plus its res / mask / bny loads,
+// which are left out of the count: a count below the true number only waits longer.
+template <int EST>
+__device__ __forceinline__ void wait_vm(bool next, int epilogues) {
+  if (next) {
+    if (epilogues == 0) vmcnt<4>();
+    else if (epilogues == 1) vmcnt<4 + EST>();
+    else vmcnt<4 + 2 * EST>();
+  } else {
+    if (epilogues == 0) vmcnt<0>();
+    else if (epilogues == 1) vmcnt<EST>();
+    else vmcnt<2 * EST>();
+  }
+}
+
+// LDS: 32 KiB of resident weight slice (AK k steps: K <= 128 at BI = 128, K <= 256 at BI = 64) + 3 x 16 KiB of
+// B stages = 80 KiB: two workgroups per CU, as gemm_kernel.
+template <bool A_COL, int BI, bool STATS, bool BNB>
+__global__ __launch_bounds__(kThreads, 2) void ring_kernel(const GemmArgs p) {
+  static_assert(!(STATS && BNB), "one statistics epilogue per launch");
+  static_assert(!A_COL || BI == 128, "the column image of the weight slice is 128 wide");
+  constexpr int BJ = 128, NS = kRingStages, AK = 256 / BI;
+  constexpr int NI = 2, WI = BI / 64, WJ = 4 / WI, NJ = BJ / (32 * WJ);
+  constexpr int AE = BI * kBK;          // one k step of the resident slice
+  constexpr int CPR = BI / 8;           // 16-B chunks per output row
+  constexpr int RPP = kThreads / CPR;   // rows per pass of the 256 threads
+  constexpr int EST = BJ / RPP;         // global stores per thread and full tile
+  constexpr int PR = kBStage / BI;      // output rows one B stage holds as [PR][BI] bf16
+  constexpr int NP = BJ / PR;           // staging passes per tile (2 at BI = 128: wave row wj writes pass wj)
+  static_assert(NP == 1 || NP == WJ, "a staging pass is the j rows of one wave row");
+  __shared__ __attribute__((aligned(16))) uint16_t smem[AK * AE + NS * kBStage];
+  uint16_t* const ares = smem;
+  uint16_t* const bring = smem + AK * AE;
+  const unsigned lds_a = (unsigned)(size_t)(lds_void*)smem, lds_b = lds_a + 2u * AK * AE;  // LDS byte addresses
+  const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wi = wave / WJ, wj = wave % WJ;
+  int wid = blockIdx.x;
+  if (p.xcd) {
+    const int n = gridDim.x, x = wid % 8, q8 = n / 8, r8 = n % 8;
+    wid = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + wid / 8;
+  }
+  const int it = wid % p.i_tiles;
+  const int grp = wid / p.i_tiles;
+  const int64_t i0 = (int64_t)it * BI;
+  const int nk = (int)(p.K / kBK);  // <= AK (launcher)
+  const int jstride = p.j_groups, jtiles = p.j_tiles;
+  int jt = grp;
+  if (jt >= jtiles) return;
+  const int total = ((jtiles - grp + jstride - 1) / jstride) * nk;  // k steps of this workgroup's stream
+  // kernel-argument fields as scalars (a lambda capturing the struct by reference sends it to scratch)
+  const uint16_t* const pb = p.b;
+  const int64_t J = p.J, ldb = p.ldb;
+
+  // resident weight slice: nk images, [BI][64] swz<64> (row memory) or [64][128] swz<128> (column memory)
+  for (int t = 0; t < nk; ++t) {
+#pragma unroll
+    for (int q = 0; q < BI / 32; ++q) {
+      const int inst = wave * (BI / 32) + q;  // 1 KiB of the image per instruction
+      unsigned off;
+      if constexpr (A_COL) {
+        const int r = inst * 4 + (lane >> 4);
+        const int ch = (lane & 15) ^ (((r & 3) << 2) | ((r >> 2) & 3));
+        off = (unsigned)((t * kBK + r) * (int)p.lda + (int)i0 + 8 * ch) * 2u;
+      } else {
+        const int r = inst * 8 + (lane >> 3);
+        const int ch = (lane & 7) ^ ((((r >> 1) & 1) << 2) | ((r >> 2) & 3));
+        off = (unsigned)(((int)i0 + r) * (int)p.lda + t * kBK + 8 * ch) * 2u;
+      }
+      glds16_off(p.a, off, lds_a + 2u * (unsigned)(t * AE + inst * 512));
+    }
+  }
+
+  // B stage: this wave's 4 DMA instructions cover rows 32 wave + 8 q + (lane >> 3); slot lane & 7 of row r
+  // holds chunk (lane & 7) ^ f(r) (swz<64>).  Rows past J load the last valid row; their outputs are skipped.
+  const int rq0 = wave * 32 + (lane >> 3);
+  unsigned colb[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = rq0 + 8 * q;
+    colb[q] = 16u * (unsigned)((lane & 7) ^ ((((r >> 1) & 1) << 2) | ((r >> 2) & 3)));
+  }
+  int ijt = grp, ikt = 0, istage = 0;  // DMA cursor: j tile, k step and stage of the next step to issue
+  auto issue_b = [&]() {
+    const int64_t j0 = (int64_t)ijt * BJ;
+    const int valid = (int)min((int64_t)BJ, J - j0);
+    const uint16_t* base = pb + j0 * ldb + (int64_t)ikt * kBK;
+    const unsigned dst = lds_b + 2u * (unsigned)(istage * kBStage + wave * 2048);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int row = min(rq0 + 8 * q, valid - 1);
+      glds16_off(base, (unsigned)(row * (int)ldb) * 2u + colb[q], dst + 1024u * q);
+    }
+    istage = istage + 1 == NS ? 0 : istage + 1;
+    if (++ikt == nk) {
+      ikt = 0;
+      ijt += jstride;
+    }
+  };
+  issue_b();
+  if (total > 1) issue_b();
+
+  f32x16 acc[NI][NJ];
+#pragma unroll
+  for (int a = 0; a < NI; ++a)
+#pragma unroll
+    for (int b = 0; b < NJ; ++b) acc[a][b] = zero16();
+  float ssum[8], ssq[8], bs[8], bh[8];
+  if constexpr (STATS || BNB) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ssum[e] = ssq[e] = 0.f;
+  }
+  if constexpr (BNB) {
+    const int cc = tid % (BI / 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      bs[e] = p.bnsc[i0 + 8 * cc + e];
+      bh[e] = p.bnsh[i0 + 8 * cc + e];
+    }
+  }
+  // byte offset of 16-B chunk c of staged output row r (gemm_kernel's images)
+  auto out_off = [](int r, int c) {
+    if constexpr (BI == 128) return r * 256 + 16 * (c ^ (r & 15));
+    else return r * 128 + 16 * (c ^ ((r >> 1) & 7));
+  };
+
+  int u = 0, t = 0, st = 0;     // stream step, its k step and its stage
+  int l1 = 0, l2 = 0;           // 1: step u-1 / u-2 ended a tile
+  for (;;) {
+    wait_vm<EST>(u + 1 < total, l1 + l2);
+    ring_bar();  // step u landed in every wave; stage (u - 1) % NS (operands or staged output) fully consumed
+    if (u + 2 < total) issue_b();  // into that stage
+    const uint16_t* abuf = ares + t * AE;
+    uint16_t* bbuf = bring + st * kBStage;
+#pragma unroll
+    for (int s = 0; s < kBK / 16; ++s) {
+      bf16x8 af[NI], bv[NJ];
+#pragma unroll
+      for (int a = 0; a < NI; ++a) af[a] = Stage<A_COL, BI>::frag(abuf, s, (wi * NI + a) * 32, lane);
+#pragma unroll
+      for (int b = 0; b < NJ; ++b) bv[b] = Stage<false, BJ>::frag(bbuf, s, (wj * NJ + b) * 32, lane);
+#pragma unroll
+      for (int a = 0; a < NI; ++a)
+#pragma unroll
+        for (int b = 0; b < NJ; ++b) acc[a][b] = mfma(af[a], bv[b], acc[a][b]);
+    }
+    const bool last = t == nk - 1;
+    if (last) {
+      // epilogue (gemm_kernel's, staged through the stage just consumed in NP passes of PR rows): the next
+      // steps' DMA stays in flight in the other two stages
+      ring_bar();  // every wave is done reading bbuf
+      char* ot = reinterpret_cast<char*>(bbuf);
+      uint16_t* out = static_cast<uint16_t*>(p.out);
+      const int c = tid % CPR;
+#pragma unroll
+      for (int h = 0; h < NP; ++h) {
+        if (NP == 1 || wj == h) {
+#pragma unroll
+          for (int b = 0; b < NJ; ++b) {
+            const int jr = (wj * NJ + b) * 32 + l32 - h * PR;
+#pragma unroll
+            for (int a = 0; a < NI; ++a)
+#pragma unroll
+              for (int g = 0; g < 4; ++g) {
+                const int ic = (wi * NI + a) * 32 + 8 * g + 4 * hh;  // first of the 4 i
+                const unsigned lo = (unsigned)f32_to_bf16(acc[a][b][4 * g]) |
+                                    ((unsigned)f32_to_bf16(acc[a][b][4 * g + 1]) << 16);
+                const unsigned hi = (unsigned)f32_to_bf16(acc[a][b][4 * g + 2]) |
+                                    ((unsigned)f32_to_bf16(acc[a][b][4 * g + 3]) << 16);
+                *reinterpret_cast<u32x2*>(ot + out_off(jr, ic >> 3) + 8 * ((ic >> 2) & 1)) = u32x2{lo, hi};
+              }
+          }
+        }
+        ring_bar();
+#pragma unroll
+        for (int uu = 0; uu < EST / NP; ++uu) {
+          const int r = tid / CPR + RPP * (h * (EST / NP) + uu);
+          const int64_t j = (int64_t)jt * BJ + r;
+          if (j < p.J) {
+            u32x4 v = *reinterpret_cast<const u32x4*>(ot + out_off(r - h * PR, c));
+            if (p.res != nullptr) {  // fused residual-gradient accumulation (fp32 add, one rounding)
+              u32x4 rv = *reinterpret_cast<const u32x4*>(p.res + j * p.ldo + i0 + 8 * c);
+              if (p.resmask != nullptr) {
+                const unsigned bits = p.resmask[(j * p.ldo + i0 + 8 * c) >> 3];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  rv[e] &= ((bits >> (2 * e)) & 1u ? 0xffffu : 0u) | ((bits >> (2 * e + 1)) & 1u ? 0xffff0000u : 0u);
+              }
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float lo = bf16_to_f32((unsigned short)(v[e] & 0xffffu)) +
+                                 bf16_to_f32((unsigned short)(rv[e] & 0xffffu));
+                const float hi = bf16_to_f32((unsigned short)(v[e] >> 16)) + bf16_to_f32((unsigned short)(rv[e] >> 16));
+                v[e] = (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16);
+              }
+            }
+            *reinterpret_cast<u32x4*>(out + j * p.ldo + i0 + 8 * c) = v;
+            if constexpr (BNB) {
+              const u32x4 yv = *reinterpret_cast<const u32x4*>(p.bny + j * p.ldo + i0 + 8 * c);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                  const int k = 2 * e + hf;
+                  const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
+                  const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
+                  const bool on = yy * bs[k] + bh[k] > 0.f;
+                  const float gm = on ? g : 0.f;
+                  ssum[k] += gm;
+                  ssq[k] += gm * yy;
+                }
+              }
+            }
+            if constexpr (STATS) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float x0 = bf16_to_f32((unsigned short)(v[e] & 0xffffu));
+                const float x1 = bf16_to_f32((unsigned short)(v[e] >> 16));
+                ssum[2 * e] += x0;
+                ssq[2 * e] += x0 * x0;
+                ssum[2 * e + 1] += x1;
+                ssq[2 * e + 1] += x1 * x1;
+              }
+            }
+          }
+        }
+        if (h + 1 < NP) ring_bar();  // pass h read back before pass h + 1 overwrites it
+      }
+#pragma unroll
+      for (int a = 0; a < NI; ++a)
+#pragma unroll
+        for (int b = 0; b < NJ; ++b) acc[a][b] = zero16();
+    }
+    if (++u == total) break;
+    l2 = l1;
+    l1 = last ? 1 : 0;
+    st = st + 1 == NS ? 0 : st + 1;
+    if (last) {
+      t = 0;
+      jt += jstride;
+    } else {
+      ++t;
+    }
+  }
+
+  if constexpr (STATS || BNB) {
+    ring_bar();  // the stream is over (the last wait was a drain): the stages are free
+    float* red = reinterpret_cast<float*>(bring);  // [RPP][2][BI]: one stage
+    const int c = tid % CPR, rg = tid / CPR;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      red[(rg * 2) * BI + 8 * c + e] = ssum[e];
+      red[(rg * 2 + 1) * BI + 8 * c + e] = ssq[e];
+    }
+    ring_bar();
+    for (int k = tid; k < 2 * BI; k += kThreads) {
+      const int which = k / BI, ii = k % BI;
+      float v = 0.f;
+      for (int g = 0; g < RPP; ++g) v += red[(g * 2 + which) * BI + ii];
+      p.stats[((int64_t)grp * 2 + which) * p.I + i0 + ii] = v;
+    }
+  }
+}
+
+template <bool A_COL, int BI, bool STATS, bool BNB = false>
+hipError_t launch_ring(const GemmArgs& p, int grid, hipStream_t s) {
+  hipLaunchKernelGGL((ring_kernel<A_COL, BI, STATS, BNB>), dim3(grid), dim3(kThreads), 0, s, p);
+  return hipGetLastError();
+}
+
+// Does a store-mode launch take the ring?  Where the weight slice fits its 32 KiB, except the shapes whose
+// per-shape A/B the ring lost (docs/PERF.md round 12): BI = 64 at K = 64, where the register-staged loop already
+// runs above 5.7 TB/s.  Everything else (K > 128 at BI = 128, the BI = 64 data grad) runs gemm_kernel.
+inline bool use_ring(bool a_col, int bi, int64_t K) {
+  if (tune().ring <= 0 || (a_col && bi != 128)) return false;
+  const int64_t nk = K / kBK;
+  return bi == 128 ? nk <= 2 : (nk >= 2 && nk <= 4);
+}
+
+// i-tile width of the forward: 128 where Cout allows, except that with the ring on K = 192 / 256 take 64-wide
+// tiles, whose weight slice fits the ring's 32 KiB (measured faster than 128-wide register-staged tiles:
+// docs/PERF.md round 12).  The plan, and with it the number of partial rows, follows the width.
+inline int fwd_bi(int64_t cin, int64_t cout) {
+  if (cout % 128 != 0) return 64;
+  const int64_t nk = cin / kBK;
+  return (tune().ring > 0 && nk >= 3 && nk <= 4) ? 64 : 128;
 }
 
 // forward / dgrad: i tiles x j groups, each workgroup walking an equal share of the j tiles.
@@ -706,9 +1045,14 @@ using namespace madnn::conv;
 
 extern "C" {
 
-// key 0: forward/dgrad grid target, 1: weight-grad workgroups, 2: XCD remap (0/1); returns the old value
+// key 0: forward/dgrad grid target, 1: weight-grad workgroups, 2: XCD remap (0/1), 3: ring main loop (0/1);
+// returns the old value (value < 0: query only)
 int madnn_conv1x1_tune(int key, int value) {
-  int* f = key == 0 ? &tune().fwd_wg : key == 1 ? &tune().wgrad_wg : key == 2 ? &tune().xcd : nullptr;
+  int* f = key == 0   ? &tune().fwd_wg
+           : key == 1 ? &tune().wgrad_wg
+           : key == 2 ? &tune().xcd
+           : key == 3 ? &tune().ring
+                      : nullptr;
   if (f == nullptr) return -1;
   const int old = *f;
   if (value >= 0) *f = value;
@@ -723,7 +1067,7 @@ int madnn_conv1x1_supported(int64_t cin, int64_t cout) {
 int madnn_conv1x1_stat_rows(int64_t M, int64_t cin, int64_t cout) {
   if (!madnn_conv1x1_supported(cin, cout) || M <= 0) return 0;
   GemmArgs p{};
-  plan_persistent(p, M, cout % 128 == 0 ? 128 : 64, cout, cin);
+  plan_persistent(p, M, fwd_bi(cin, cout), cout, cin);
   return p.j_groups;
 }
 
@@ -751,13 +1095,16 @@ hipError_t madnn_conv1x1_fwd(const void* x, const void* w, void* y, float* stats
   p.I = cout;
   p.J = M;
   p.K = cin;
-  const bool wide = cout % 128 == 0;
+  const bool wide = fwd_bi(cin, cout) == 128;
   plan_persistent(p, M, wide ? 128 : 64, cout, cin);
   const int grid = p.i_tiles * p.j_groups;
+  const bool ring = use_ring(false, wide ? 128 : 64, cin);
   if (wide) {
+    if (ring) return stats ? launch_ring<false, 128, true>(p, grid, s) : launch_ring<false, 128, false>(p, grid, s);
     return stats ? launch<false, false, 128, 128, kStoreT, true>(p, grid, s)
                  : launch<false, false, 128, 128, kStoreT, false>(p, grid, s);
   }
+  if (ring) return stats ? launch_ring<false, 64, true>(p, grid, s) : launch_ring<false, 64, false>(p, grid, s);
   return stats ? launch<false, false, 64, 128, kStoreT, true>(p, grid, s)
                : launch<false, false, 64, 128, kStoreT, false>(p, grid, s);
 }
@@ -787,15 +1134,18 @@ hipError_t madnn_conv1x1_dgrad(const void* dy, const void* w, void* dx, const vo
   const bool wide = cin % 128 == 0;
   plan_persistent(p, M, wide ? 128 : 64, cin, cout);
   const int grid = p.i_tiles * p.j_groups;
+  const bool ring = use_ring(true, wide ? 128 : 64, cout);
   if (bny != nullptr) {
     if (partial == nullptr || bnsc == nullptr || bnsh == nullptr || res != nullptr) return hipErrorInvalidValue;
     p.bny = static_cast<const uint16_t*>(bny);
     p.bnsc = bnsc;
     p.bnsh = bnsh;
     p.stats = partial;
+    if (ring) return launch_ring<true, 128, false, true>(p, grid, s);
     return wide ? launch<true, false, 128, 128, kStoreT, false, true>(p, grid, s)
                 : launch<true, false, 64, 128, kStoreT, false, true>(p, grid, s);
   }
+  if (ring) return launch_ring<true, 128, false>(p, grid, s);
   return wide ? launch<true, false, 128, 128, kStoreT, false>(p, grid, s)
               : launch<true, false, 64, 128, kStoreT, false>(p, grid, s);
 }
