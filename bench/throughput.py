@@ -23,7 +23,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def build(name, meta: bool):
+def build(name, meta: bool, dropout: float = 0.0):
     from madnn.models import MLP, resnet50
     from madnn.models.bert import BertForPreTraining, bert_config
     from madnn.models.gpt2 import GPT2, gpt2_config
@@ -34,9 +34,9 @@ def build(name, meta: bool):
         if name == "resnet50":
             return resnet50()
         if name.startswith("gpt2"):
-            return GPT2(gpt2_config(name))
+            return GPT2(gpt2_config(name, dropout=dropout))
         if name.startswith("bert"):
-            return BertForPreTraining(bert_config(name))
+            return BertForPreTraining(bert_config(name, dropout=dropout))
         if name.startswith("llama3"):
             return Llama(llama_config(name))
         if name == "mlp":
@@ -57,6 +57,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--meta-init", action="store_true", help="build on the meta device (8B models)")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="gpt2* / bert*: the config's dropout (hidden, embedding and attention), e.g. 0.1")
     ap.add_argument("--metrics", default=None, help="after timing, run 3 metered steps (JSONL to this path)")
     a = ap.parse_args()
 
@@ -68,7 +70,7 @@ def main():
     dev = madnn.device()
     torch.manual_seed(0)
     meta = a.meta_init or a.model == "llama3-8b"
-    model = build(a.model, meta)
+    model = build(a.model, meta, a.dropout)
     opt = (FusedAdam(model.parameters(), lr=1e-4, weight_decay=0.01) if a.optimizer == "adam"
            else FusedSGD(model.parameters(), lr=0.1, momentum=0.9))
     image = a.model == "resnet50" or a.model == "mlp"
@@ -136,6 +138,10 @@ def main():
            "ms_per_step": round(dt / a.steps * 1e3, 2), "plan": plan.describe() if plan is not None else "dp",
            "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 1e9, 2), "dtype": "bf16",
            "data": "synthetic", "loss": float(loss) if loss is not None else None}
+    if a.dropout:
+        from madnn import ops
+
+        out.update(dropout=a.dropout, hidden_dropout_fused=bool(ops.HIDDEN_DROPOUT))
     if metered is not None:
         out["metrics"] = {k: round(v, 3) if isinstance(v, float) else v for k, v in metered.items()}
     if rank == 0:

@@ -66,8 +66,11 @@ class BertEmbed(nn.Module):
             raise ValueError(f"sequence length {ids.size(1)} exceeds max_position {self.position.num_embeddings}")
         pos = torch.arange(ids.size(1), device=ids.device)
         # single-segment synthetic input: token type 0 for every position
-        x = self.word(ids) + (self.position(pos) + self.token_type.weight[0])
-        return self.drop(self.norm(x))
+        x = self.norm(self.word(ids) + (self.position(pos) + self.token_type.weight[0]))
+        p = self.drop.p if self.training else 0.0
+        if p > 0.0 and ops.hidden_dropout_supported(x, x.size(-1), p):
+            return ops.dropout_add(x, None, p)   # K16: the mask is generated in the kernel
+        return self.drop(x)
 
 
 class BertLayer(nn.Module):
@@ -84,7 +87,10 @@ class BertLayer(nn.Module):
         return [(("fc1",), "fc2")]
 
     def forward(self, x):
-        fused = (self.drop.p == 0.0 or not self.training) and ops.FUSED_LINEAR
+        p = self.drop.p if self.training else 0.0
+        if p > 0.0 and ops.hidden_dropout_supported(x, x.size(-1), p):
+            return self._forward_drop(x, p)
+        fused = p == 0.0 and ops.FUSED_LINEAR
         if fused and type(self.attn) is SelfAttention:
             # LN(x + attn(x)): x's residual gradient is summed inside the QKV projection's data-gradient
             # GEMM (ops.linear_tee), not by a separate pass over x's two gradients
@@ -100,6 +106,24 @@ class BertLayer(nn.Module):
             return self.ffn_norm(h)
         h = self.drop(linear(self.fc2, F.gelu(linear(self.fc1, y))))
         z, _ = self.ffn_norm(h, residual=y)
+        return z
+
+    def _forward_drop(self, x, p):
+        """Training with hidden dropout: both dropouts run inside the two LayerNorm kernels (K3 with
+        ``dropout_p``), so the fused paths of the dropout-free layer stay: ``forward_tee`` and the
+        one-node MLP.  The MLP's residual y is added by ffn_norm (after the dropout), so y gets two
+        gradients that autograd sums."""
+        if ops.FUSED_LINEAR and type(self.attn) is SelfAttention:
+            a, xr = self.attn.forward_tee(x)
+        else:
+            a, xr = self.attn(x), x
+        y, _ = self.attn_norm(a, residual=xr, dropout_p=p)
+        if ops.FUSED_LINEAR and type(self.fc1) is nn.Linear and type(self.fc2) is nn.Linear:
+            h = ops.gelu_mlp(y, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, residual=None,
+                             approximate="none")
+        else:
+            h = linear(self.fc2, F.gelu(linear(self.fc1, y)))
+        z, _ = self.ffn_norm(h, residual=y, dropout_p=p)
         return z
 
 

@@ -63,7 +63,11 @@ class GPT2Embed(nn.Module):
         if ids.size(1) > self.wpe.num_embeddings:   # host-side: an out-of-range gather faults the GPU
             raise ValueError(f"sequence length {ids.size(1)} exceeds n_positions {self.wpe.num_embeddings}")
         pos = torch.arange(ids.size(1), device=ids.device)
-        return self.drop(self.wte(ids) + self.wpe(pos))
+        x = self.wte(ids) + self.wpe(pos)
+        p = self.drop.p if self.training else 0.0
+        if p > 0.0 and ops.hidden_dropout_supported(x, x.size(-1), p):
+            return ops.dropout_add(x, None, p)   # K16: the mask is generated in the kernel
+        return self.drop(x)
 
 
 class GPT2MLP(nn.Module):
@@ -76,11 +80,19 @@ class GPT2MLP(nn.Module):
     def forward(self, x, residual=None):
         """MLP(x) (+ ``residual``, added in c_proj's GEMM epilogue when dropout is off).  Plain
         ``nn.Linear`` layers run as ONE fused autograd node (``ops.gelu_mlp``): the GELU and its
-        backward live in the two GEMMs' epilogues."""
+        backward live in the two GEMMs' epilogues.  With dropout on, the node stays and the dropout
+        and the residual add are one K16 pass (``ops.dropout_add``)."""
         no_drop = self.drop.p == 0.0 or not self.training
-        if no_drop and ops.FUSED_LINEAR and type(self.c_fc) is nn.Linear and type(self.c_proj) is nn.Linear:
+        plain = ops.FUSED_LINEAR and type(self.c_fc) is nn.Linear and type(self.c_proj) is nn.Linear
+        if no_drop and plain:
             return ops.gelu_mlp(x, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias,
                                 residual)
+        if not no_drop and ops.hidden_dropout_supported(x, self.c_proj.out_features, self.drop.p):
+            if plain:
+                m = ops.gelu_mlp(x, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias, None)
+            else:
+                m = linear(self.c_proj, linear(self.c_fc, x, gelu=True))
+            return ops.dropout_add(m, residual, self.drop.p)
         if residual is not None and no_drop:
             return linear(self.c_proj, linear(self.c_fc, x, gelu=True), residual=residual)
         y = self.drop(linear(self.c_proj, linear(self.c_fc, x, gelu=True)))
@@ -101,6 +113,11 @@ class GPT2Block(nn.Module):
 
     def forward(self, x):
         y, xr = self.ln_1(x, fork=True)       # xr aliases x: its gradient joins ln_1's backward pass
+        p = self.drop.p if self.training else 0.0
+        if p > 0.0 and ops.hidden_dropout_supported(x, x.size(-1), p):
+            # h = x + dropout(a), y = LN(h): still one kernel, the mask is generated inside it
+            y, h = self.ln_2(self.attn(y), residual=xr, dropout_p=p)
+            return self.mlp(y, residual=h)    # h + dropout(MLP(y)): one K16 pass after the fused MLP node
         a = self.drop(self.attn(y))
         y, h = self.ln_2(a, residual=xr)     # h = x + a, y = LN(h): one kernel
         return self.mlp(y, residual=h)        # h + MLP(y): the add rides in c_proj's GEMM epilogue

@@ -37,12 +37,16 @@ class FusedLayerNorm(nn.Module):
             if self.bias is not None:
                 self.bias.zero_()
 
-    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, fork: bool = False):
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, fork: bool = False,
+                dropout_p: float = 0.0):
         """LN(x); with ``residual``, (LN(x + residual), x + residual) in one kernel; with ``fork``,
-        (LN(x), x) whose second output's gradient joins x's inside the LN backward pass."""
+        (LN(x), x) whose second output's gradient joins x's inside the LN backward pass.
+        ``dropout_p`` (training mode only, needs ``residual``): x is dropped before the add, inside the
+        same kernel on HIP tensors (see :func:`madnn.ops.layer_norm`)."""
         if residual is not None and residual.dtype != x.dtype:
             residual = residual.to(x.dtype)
-        return ops.layer_norm(x, self.weight, self.bias, self.eps, residual=residual, fork=fork)
+        return ops.layer_norm(x, self.weight, self.bias, self.eps, residual=residual, fork=fork,
+                              dropout_p=dropout_p if self.training else 0.0)
 
     def extra_repr(self):
         return f"{self.normalized_shape}, eps={self.eps}, kernel=madnn.K3"
@@ -58,10 +62,13 @@ class FusedRMSNorm(nn.Module):
         with torch.no_grad():
             self.weight.fill_(1.0)
 
-    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, fork: bool = False):
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, fork: bool = False,
+                dropout_p: float = 0.0):
+        """``dropout_p`` as in :class:`FusedLayerNorm` (training mode only, needs ``residual``)."""
         if residual is not None and residual.dtype != x.dtype:
             residual = residual.to(x.dtype)
-        return ops.rms_norm(x, self.weight, self.eps, residual=residual, fork=fork)
+        return ops.rms_norm(x, self.weight, self.eps, residual=residual, fork=fork,
+                            dropout_p=dropout_p if self.training else 0.0)
 
     def extra_repr(self):
         return f"{self.weight.numel()}, eps={self.eps}, kernel=madnn.K3"

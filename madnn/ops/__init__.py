@@ -225,7 +225,61 @@ def _from_biased_linear(x: torch.Tensor) -> bool:
     return _linear_bias_dtype(x) is not None
 
 
-def _norm(x, weight, bias, eps, rms, residual, fork=False):
+class _NormDropFn(torch.autograd.Function):
+    """K3 residual mode with hidden dropout on the normed branch: s = res + rp * m * x, y = N(s), the
+    mask m generated in the kernel (``reference.hidden_dropout_mask``) and regenerated in the backward,
+    which returns two distinct gradients: rp * m * dh for x and dh for the residual.  The column sums
+    for a producing Linear's bias gradient (see :class:`_NormFn`) are those of x's gradient."""
+
+    @staticmethod
+    def forward(ctx, x, res, w, b, eps, rms, p, seed, offset):
+        shape = x.shape
+        y, s, mean, rstd = _need_native("norm_drop_fwd").norm_drop_fwd(x.contiguous(), res.contiguous(), w, b,
+                                                                       float(eps), bool(rms), p, seed, offset)
+        ctx.save_for_backward(s, w, mean, rstd)
+        ctx.colsum = NORM_COLSUM and _from_biased_linear(x)
+        ctx.colsum_bf16 = ctx.colsum and _linear_bias_dtype(x) == torch.bfloat16
+        ctx.rms = rms
+        ctx.has_bias = b is not None
+        ctx.drop = (p, seed, offset)   # the backward kernel regenerates the mask from these
+        ctx.shape = shape
+        return y.view(shape), s.view(shape)
+
+    @staticmethod
+    def backward(ctx, dy, ds):
+        s, w, mean, rstd = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(s)
+        dx, dh, dw, db, cs = torch.ops.madnn.norm_drop_bwd(dy.contiguous().view(s.shape), s, w, mean, rstd,
+                                                           ds.contiguous().view(s.shape) if ds is not None else None,
+                                                           ctx.rms, ctx.has_bias, ctx.colsum, ctx.colsum_bf16,
+                                                           *ctx.drop)
+        dx = dx.view(ctx.shape)
+        if ctx.colsum:
+            _attach(dx, "_madnn_colsum", cs)
+        return dx, dh.view(ctx.shape), dw, (db if ctx.has_bias else None), None, None, None, None, None
+
+
+HIDDEN_DROPOUT = os.environ.get("MADNN_HIDDEN_DROPOUT", "1") != "0"  # K3 DROP / K16 (0: nn.Dropout, as before)
+
+
+def hidden_dropout_supported(t: torch.Tensor, h: int, dropout: float) -> bool:
+    """Hidden (residual) dropout with ``dropout > 0`` runs inside the kernels (K3 with
+    ``dropout_p``, K16 :func:`dropout_add`): a HIP tensor, a hidden size K3 takes, dropout in [0, 1),
+    ``MADNN_HIDDEN_DROPOUT`` on and no stream capture in progress (the host-side draw of the generator
+    offset cannot be captured).  Everything else composes ``F.dropout`` with the existing ops."""
+    return (t.device.type == "cuda" and hidden_supported(h) and 0.0 <= dropout < 1.0 and HIDDEN_DROPOUT
+            and not torch.cuda.is_current_stream_capturing())
+
+
+def _norm(x, weight, bias, eps, rms, residual, fork=False, dropout_p=0.0, rng=None):
+    if dropout_p != 0.0:
+        if residual is None or fork:
+            raise ValueError("madnn norm: dropout_p needs a residual (it drops x before x + residual) "
+                             "and cannot be combined with fork")
+        if hidden_dropout_supported(x, x.size(-1), dropout_p) and weight is not None:
+            return _NormDropFn.apply(x, residual, weight, bias, eps, rms, *_dropout_args(x, dropout_p, rng))
+        x = F.dropout(x, dropout_p, True)   # torch's own mask, then the existing norm
     if _is_dev(x):
         if weight is None:
             raise ValueError("madnn norm kernels need an affine weight")
@@ -235,17 +289,62 @@ def _norm(x, weight, bias, eps, rms, residual, fork=False):
     return (y, x) if (fork and residual is None) else y
 
 
-def layer_norm(x, weight, bias=None, eps: float = 1e-5, residual: Optional[torch.Tensor] = None, fork: bool = False):
+def layer_norm(x, weight, bias=None, eps: float = 1e-5, residual: Optional[torch.Tensor] = None, fork: bool = False,
+               dropout_p: float = 0.0, rng=None):
     """LayerNorm over the last dim.  With ``residual``: returns (LN(x + residual), x + residual).
     With ``fork``: returns (LN(x), x) where the second output's gradient is summed into x's
-    inside the LN backward kernel (use it as the block's residual path)."""
-    return _norm(x, weight, bias, eps, False, residual, fork)
+    inside the LN backward kernel (use it as the block's residual path).
+    ``dropout_p > 0`` (needs ``residual``): x is dropped first, s = residual + dropout(x), and
+    (LN(s), s) is returned; on HIP tensors the mask is generated inside the K3 kernel
+    (:func:`reference.hidden_dropout_mask`; ``rng = (seed, offset)`` pins it, by default it is drawn
+    from torch's device generator), elsewhere ``F.dropout`` runs in front of the norm."""
+    return _norm(x, weight, bias, eps, False, residual, fork, dropout_p, rng)
 
 
-def rms_norm(x, weight, eps: float = 1e-6, residual: Optional[torch.Tensor] = None, fork: bool = False):
+def rms_norm(x, weight, eps: float = 1e-6, residual: Optional[torch.Tensor] = None, fork: bool = False,
+             dropout_p: float = 0.0, rng=None):
     """RMSNorm over the last dim.  With ``residual``: returns (RMS(x + residual), x + residual);
-    with ``fork``: (RMS(x), x) as in :func:`layer_norm`."""
-    return _norm(x, weight, None, eps, True, residual, fork)
+    with ``fork``: (RMS(x), x) as in :func:`layer_norm`; ``dropout_p`` / ``rng`` as there."""
+    return _norm(x, weight, None, eps, True, residual, fork, dropout_p, rng)
+
+
+# ---------------------------------------------------------------------- K16
+class _DropoutAddFn(torch.autograd.Function):
+    """residual + rp * m * x (K16), the mask regenerated in the backward: dx = rp * m * g, and the
+    residual's gradient is g itself (no copy)."""
+
+    @staticmethod
+    def forward(ctx, x, res, p, seed, offset):
+        ctx.drop = (p, seed, offset)
+        ctx.has_res = res is not None
+        return torch.ops.madnn.dropout_add(x, res, p, seed, offset)
+
+    @staticmethod
+    def backward(ctx, g):
+        gc = g.contiguous()
+        if gc.data_ptr() % 16:
+            gc = gc.clone()   # K16 moves 16 B per lane: a fresh (aligned) buffer
+        return torch.ops.madnn.dropout_add(gc, None, *ctx.drop), (g if ctx.has_res else None), None, None, None
+
+
+def dropout_add(x: torch.Tensor, residual: Optional[torch.Tensor] = None, p: float = 0.0, rng=None) -> torch.Tensor:
+    """``residual + dropout(x, p)`` (``dropout(x, p)`` without a residual) for the places where no norm
+    follows.  Contiguous bf16 / fp32 HIP tensors with a last dim that is a multiple of 8 run K16 in one
+    pass with the hidden-dropout mask generated in the kernel (``rng`` as in :func:`layer_norm`);
+    anything else composes ``F.dropout`` and an add."""
+    if p == 0.0:
+        return x + residual if residual is not None else x
+    if residual is not None and residual.dtype != x.dtype:
+        residual = residual.to(x.dtype)
+    if (x.dim() >= 1 and hidden_dropout_supported(x, x.size(-1), p) and x.dtype in (torch.bfloat16, torch.float32)
+            and x.numel() > 0 and (residual is None or residual.shape == x.shape)):
+        xc = x.contiguous()
+        rc = residual.contiguous() if residual is not None else None
+        if xc.data_ptr() % 16 == 0 and (rc is None or rc.data_ptr() % 16 == 0):
+            _need_native("dropout_add")
+            return _DropoutAddFn.apply(xc, rc, *_dropout_args(x, p, rng))
+    y = F.dropout(x, p, True)
+    return y + residual if residual is not None else y
 
 
 def _attach(t: torch.Tensor, name: str, value) -> None:
@@ -630,16 +729,19 @@ def attention_supported(t: torch.Tensor, head_dim: int, dropout: float = 0.0) ->
     return dropout == 0.0 or (ATTN_DROPOUT and not torch.cuda.is_current_stream_capturing())
 
 
-def _attn_dropout_args(t: torch.Tensor, dropout_p: float, rng) -> tuple:
-    """``(p, seed, offset)`` of one K8 call, seed / offset as the signed 64-bit values the op schema
-    takes.  ``rng=None`` draws from torch's generator of the tensor's device and advances its offset,
-    so ``torch.manual_seed`` reproduces a run, ``torch.utils.checkpoint``'s RNG preservation replays
-    the same mask in the recompute, and checkpointed RNG streams cover it with no new state."""
+def _dropout_args(t: torch.Tensor, dropout_p: float, rng, gen=None) -> tuple:
+    """``(p, seed, offset)`` of one call of a kernel that generates its dropout mask itself (K8, K3
+    DROP, K16), seed / offset as the signed 64-bit values the op schemas take.  ``rng=None`` draws
+    from torch's generator of the tensor's device (``gen``: that generator, for tests) and advances its
+    offset by 4, so ``torch.manual_seed`` reproduces a run, ``torch.utils.checkpoint``'s RNG
+    preservation replays the same mask in the recompute, and checkpointed RNG streams cover it with
+    no new state."""
     if dropout_p == 0.0:
         return 0.0, 0, 0
     reference.attention_dropout_threshold(dropout_p)   # raises for a p that keeps nothing
     if rng is None:
-        gen = torch.cuda.default_generators[t.device.index]
+        if gen is None:
+            gen = torch.cuda.default_generators[t.device.index]
         seed, offset = gen.initial_seed(), gen.get_offset()
         gen.set_offset(offset + 4)
     else:
@@ -656,7 +758,7 @@ def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dr
     scale = scale if scale is not None else q.size(-1) ** -0.5
     if attention_supported(q, q.size(-1), dropout_p):
         _need_native("attention")
-        return _AttnFn.apply(q, k, v, causal, scale, *_attn_dropout_args(q, dropout_p, rng))
+        return _AttnFn.apply(q, k, v, causal, scale, *_dropout_args(q, dropout_p, rng))
     return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p)
 
 
@@ -668,7 +770,7 @@ def attention_qkvpacked(qkv, heads: int, kv_heads: int, *, causal: bool = True, 
     scale = scale if scale is not None else d ** -0.5
     if attention_supported(qkv, d, dropout_p) and qkv.is_contiguous():
         _need_native("attention")
-        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_attn_dropout_args(qkv, dropout_p, rng))
+        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_dropout_args(qkv, dropout_p, rng))
     q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
     return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p)
 
@@ -2116,7 +2218,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 
 __all__ = [
     "bucket_pack", "bucket_unpack", "flat_scale_cast", "sgd_step", "adam_step", "grad_norm", "layer_norm",
-    "rms_norm", "batch_norm_act", "bn_supported", "cross_entropy", "attention", "attention_qkvpacked", "attention_supported",
+    "rms_norm", "dropout_add", "hidden_dropout_supported", "batch_norm_act", "bn_supported", "cross_entropy", "attention", "attention_qkvpacked", "attention_supported",
     "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
     "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
     "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",

@@ -56,6 +56,7 @@
 
 #include "attn.h"
 #include "common.h"
+#include "dropout.h"
 
 namespace madnn {
 namespace attn {
@@ -224,35 +225,7 @@ __device__ __forceinline__ void store4_bf16(uint16_t* p, float a, float b, float
 }
 
 // ------------------------------------------------------------------ dropout mask
-constexpr int kPhiloxRounds = 10;
-
-struct DropRng {
-  uint32_t k0, k1, c0;  // Philox key, counter word 0
-};
-
-__device__ __forceinline__ DropRng drop_rng(uint64_t seed, uint64_t offset) {
-  return DropRng{(uint32_t)seed, (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32), (uint32_t)offset};
-}
-
-// The 16 mask bytes of head bh's 4 x 4 block (queries 4 qb..4 qb + 3) x (keys 4 kb..4 kb + 3):
-// Philox4x32 on the counter (c0, bh, qb, kb); word = query & 3, byte = key & 3.
-__device__ __forceinline__ u32x4 drop_block(const DropRng& g, uint32_t bh, uint32_t qb, uint32_t kb) {
-  uint32_t c0 = g.c0, c1 = bh, c2 = qb, c3 = kb, k0 = g.k0, k1 = g.k1;
-#pragma unroll
-  for (int r = 0; r < kPhiloxRounds; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return u32x4{c0, c1, c2, c3};
-}
-
-__device__ __forceinline__ uint32_t drop_byte(uint32_t word, int i) { return (word >> (8 * i)) & 0xffu; }
+// (DropRng, drop_rng, drop_block, drop_byte: dropout.h, shared with K3 and K16)
 
 // v of lane j of this lane's quad (DPP quad_perm [j, j, j, j]); j a constant after unrolling
 __device__ __forceinline__ uint32_t quad_bcast(uint32_t v, int j) {

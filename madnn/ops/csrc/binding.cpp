@@ -50,6 +50,13 @@ int64_t madnn_attn_colsum_rows(int, int);
 hipError_t madnn_attn_colsum_finalize(const float*, int64_t, int64_t, void*, int, hipStream_t);
 int madnn_attn_dropout_threshold(double);
 hipError_t madnn_attn_dropout_mask(uint8_t*, int, int, int, uint32_t, uint64_t, uint64_t, hipStream_t);
+hipError_t madnn_norm_drop_fwd(const void*, const void*, const void*, const void*, void*, void*, float*, float*, int64_t,
+                               int, float, int, int, int, uint32_t, uint64_t, uint64_t, hipStream_t);
+hipError_t madnn_norm_drop_bwd(const void*, const void*, const void*, const float*, const float*, const void*, void*,
+                               void*, void*, void*, void*, int, float*, int64_t, int, int, int, int, uint32_t, uint64_t,
+                               uint64_t, hipStream_t);
+hipError_t madnn_dropout_add(const void*, const void*, void*, int64_t, int, int, uint32_t, uint64_t, uint64_t, hipStream_t);
+hipError_t madnn_hidden_dropout_mask(uint8_t*, int64_t, int, int64_t, uint32_t, uint64_t, uint64_t, hipStream_t);
 int madnn_maxpool_supported(int64_t, int, int);
 hipError_t madnn_maxpool_fwd(const void*, void*, void*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 int madnn_pool_bn_supported(int64_t, int);
@@ -1614,6 +1621,109 @@ at::Tensor attn_dropout_mask(int64_t B, int64_t H, int64_t S, double p, int64_t 
   return out;
 }
 
+// ---- hidden dropout: K3 DROP, K16 (the mask of dropout.h; threshold / rp as K8's) ----
+// K3 forward with dropout on the normed branch: s = res + rp * m * x, y = norm(s); returns (y, s, mean, rstd)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> norm_drop_fwd(const at::Tensor& x, const at::Tensor& res,
+                                                                         const at::Tensor& w,
+                                                                         const c10::optional<at::Tensor>& b, double eps,
+                                                                         bool rms, double p, int64_t seed,
+                                                                         int64_t offset) {
+  check_dev(x, "x");
+  check_dev(res, "residual");
+  TORCH_CHECK(x.is_contiguous(), "norm input must be contiguous");
+  const int64_t H = w.numel();
+  TORCH_CHECK(x.size(-1) == H && w.is_contiguous(), "norm weight / hidden size mismatch");
+  TORCH_CHECK(H % 8 == 0 && H <= 16384, "madnn norm kernel needs H % 8 == 0 and H <= 16384, got ", H);
+  TORCH_CHECK(res.sizes() == x.sizes() && res.is_contiguous() && res.scalar_type() == x.scalar_type(),
+              "residual must match x");
+  if (b.has_value()) TORCH_CHECK(b->numel() == H && b->scalar_type() == w.scalar_type(), "norm bias mismatch");
+  const uint32_t thr = attn_drop_threshold(p);
+  const int64_t rows = x.numel() / H;
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  at::Tensor y = at::empty_like(x), sum = at::empty_like(x);
+  auto fopts = x.options().dtype(at::kFloat);
+  at::Tensor mean = rms ? at::empty({0}, fopts) : at::empty({rows}, fopts);
+  at::Tensor rstd = at::empty({rows}, fopts);
+  check(madnn_norm_drop_fwd(x.data_ptr(), res.data_ptr(), w.data_ptr(), b.has_value() ? b->data_ptr() : nullptr,
+                            y.data_ptr(), sum.data_ptr(), rms ? nullptr : mean.data_ptr<float>(),
+                            rstd.data_ptr<float>(), rows, (int)H, (float)eps, rms ? 1 : 0, dt_code(x), dt_code(w), thr,
+                            (uint64_t)seed, (uint64_t)offset, cur_stream(x)),
+        "norm_drop_fwd");
+  return {y, sum, mean, rstd};
+}
+
+// K3 backward of norm_drop_fwd (x = the saved s): returns (dx = rp * m * dh, dres = dh, dw, db, colsum of dx)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> norm_drop_bwd(
+    const at::Tensor& dy, const at::Tensor& x, const at::Tensor& w, const at::Tensor& mean, const at::Tensor& rstd,
+    const c10::optional<at::Tensor>& dres, bool rms, bool has_bias, bool colsum, bool colsum_bf16, double p,
+    int64_t seed, int64_t offset) {
+  check_dev(x, "x");
+  const int64_t H = w.numel();
+  const int64_t rows = x.numel() / H;
+  TORCH_CHECK(dy.is_contiguous() && x.is_contiguous() && dy.sizes() == x.sizes(), "norm_drop_bwd: dy/x mismatch");
+  TORCH_CHECK(H % 8 == 0 && H <= 16384 && rstd.numel() == rows && (rms || mean.numel() == rows),
+              "norm_drop_bwd: hidden size / statistics mismatch");
+  const uint32_t thr = attn_drop_threshold(p);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  at::Tensor dyc = dy.scalar_type() == x.scalar_type() ? dy : dy.to(x.scalar_type());
+  at::Tensor dx = at::empty_like(x), dh = at::empty_like(x);
+  at::Tensor dw = at::empty_like(w);
+  at::Tensor db = has_bias ? at::empty_like(w) : at::empty({0}, w.options());
+  // the partial rows hold 3 column sums with colsum, else 2 (madnn_norm_bwd_workspace counts 3)
+  at::Tensor ws = at::empty({madnn_norm_bwd_workspace(rows, (int)H) / 3 * (colsum ? 3 : 2)}, x.options().dtype(at::kFloat));
+  at::Tensor dr;
+  if (dres.has_value() && dres->defined()) {
+    TORCH_CHECK(dres->sizes() == x.sizes(), "norm_drop_bwd: dres/x mismatch");
+    dr = dres->scalar_type() == x.scalar_type() ? dres->contiguous() : dres->to(x.scalar_type()).contiguous();
+  }
+  const auto cdt = colsum_bf16 ? at::kBFloat16 : at::kFloat;
+  at::Tensor cs = colsum ? at::empty({H}, x.options().dtype(cdt)) : at::empty({0}, x.options().dtype(cdt));
+  check(madnn_norm_drop_bwd(dyc.data_ptr(), x.data_ptr(), w.data_ptr(), rms ? nullptr : mean.data_ptr<float>(),
+                            rstd.data_ptr<float>(), dr.defined() ? dr.data_ptr() : nullptr, dh.data_ptr(),
+                            dx.data_ptr(), dw.data_ptr(), has_bias ? db.data_ptr() : nullptr,
+                            colsum ? cs.data_ptr() : nullptr, colsum_bf16 ? 1 : 0, ws.data_ptr<float>(), rows, (int)H,
+                            rms ? 1 : 0, dt_code(x), dt_code(w), thr, (uint64_t)seed, (uint64_t)offset, cur_stream(x)),
+        "norm_drop_bwd");
+  return {dx, dh, dw, db, cs};
+}
+
+// K16: res + rp * m * x (res absent: rp * m * x; also the backward, on the output gradient).
+// x: contiguous bf16 / fp32 [..., H], H % 8 == 0, 16-byte aligned
+at::Tensor dropout_add(const at::Tensor& x, const c10::optional<at::Tensor>& res, double p, int64_t seed,
+                       int64_t offset) {
+  check_dev(x, "x");
+  TORCH_CHECK((x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat) && x.is_contiguous() && x.dim() >= 1 &&
+                  x.size(-1) % 8 == 0 && x.size(-1) > 0 && x.size(-1) < (1ll << 31),
+              "dropout_add: x must be contiguous bf16 / fp32 with a last dim that is a multiple of 8");
+  check_aligned16(x, "dropout_add", "x");
+  const bool has_res = res.has_value() && res->defined();
+  if (has_res) {
+    check_dev(*res, "residual");
+    TORCH_CHECK(res->sizes() == x.sizes() && res->is_contiguous() && res->scalar_type() == x.scalar_type(),
+                "dropout_add: residual must match x");
+    check_aligned16(*res, "dropout_add", "residual");
+  }
+  const uint32_t thr = attn_drop_threshold(p);
+  const int64_t H = x.size(-1), rows = x.numel() / H;
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  at::Tensor out = at::empty_like(x);
+  check(madnn_dropout_add(x.data_ptr(), has_res ? res->data_ptr() : nullptr, out.data_ptr(), rows, (int)H, dt_code(x),
+                          thr, (uint64_t)seed, (uint64_t)offset, cur_stream(x)),
+        "dropout_add");
+  return out;
+}
+
+// The hidden-dropout mask of rows row0 .. row0 + rows - 1 as a tensor: uint8 [rows, H], 1 = kept (tests)
+at::Tensor hidden_dropout_mask(int64_t rows, int64_t H, double p, int64_t seed, int64_t offset, int64_t row0) {
+  TORCH_CHECK(rows >= 0 && H > 0 && H < (1ll << 31) && row0 >= 0, "hidden_dropout_mask: shape");
+  const uint32_t thr = attn_drop_threshold(p);
+  at::Tensor out = at::empty({rows, H}, at::TensorOptions().device(at::kCUDA).dtype(at::kByte));
+  check(madnn_hidden_dropout_mask(out.data_ptr<uint8_t>(), rows, (int)H, row0, thr, (uint64_t)seed, (uint64_t)offset,
+                                  cur_stream(out)),
+        "hidden_dropout_mask");
+  return out;
+}
+
 // Hardware-queue aliasing probe (probe.hip): bounded flag wait / flag set on the current stream.
 void hwq_wait(const at::Tensor& flag, int64_t expect, int64_t timeout_us, at::Tensor out) {
   check_dev(flag, "flag");
@@ -1695,6 +1805,15 @@ TORCH_LIBRARY(madnn, m) {
       "attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, "
       "Tensor(c!) dv, bool causal, float scale, Tensor(d!)? colsum=None, float p=0.0, int seed=0, int offset=0) -> ()");
   m.def("attn_dropout_mask(int B, int H, int S, float p, int seed, int offset) -> Tensor", &attn_dropout_mask);
+  m.def("hidden_dropout_mask(int rows, int H, float p, int seed, int offset, int row0=0) -> Tensor",
+        &hidden_dropout_mask);
+  m.def(
+      "norm_drop_fwd(Tensor x, Tensor res, Tensor w, Tensor? b, float eps, bool rms, float p, int seed, int offset) -> "
+      "(Tensor, Tensor, Tensor, Tensor)");
+  m.def(
+      "norm_drop_bwd(Tensor dy, Tensor x, Tensor w, Tensor mean, Tensor rstd, Tensor? dres, bool rms, bool has_bias, "
+      "bool colsum, bool colsum_bf16, float p, int seed, int offset) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("dropout_add(Tensor x, Tensor? res, float p, int seed, int offset) -> Tensor");
   m.def("conv1x1_fwd(Tensor x, Tensor w, bool stats) -> (Tensor, Tensor)");
   m.def("conv1x1_dgrad(Tensor dy, Tensor w, Tensor? res=None, Tensor? resmask=None) -> Tensor");
   m.def("conv1x1_dgrad_bnb(Tensor dy, Tensor w, Tensor bny, Tensor scale, Tensor shift) -> (Tensor, Tensor)");
@@ -1776,6 +1895,9 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("grad_norm", grad_norm);
   m.impl("norm_fwd", norm_fwd);
   m.impl("norm_bwd", norm_bwd);
+  m.impl("norm_drop_fwd", norm_drop_fwd);
+  m.impl("norm_drop_bwd", norm_drop_bwd);
+  m.impl("dropout_add", dropout_add);
   m.impl("bn_fwd", bn_fwd);
   m.impl("bn_bwd", bn_bwd);
   m.impl("bn_fwd_dual", bn_fwd_dual);

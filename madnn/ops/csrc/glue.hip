@@ -1,4 +1,5 @@
-// K14 / K15 — the Llama block's elementwise glue as single passes (bf16 I/O, fp32 math).
+// K14 / K15 — the Llama block's elementwise glue as single passes (bf16 I/O, fp32 math);
+// K16 — hidden dropout (+ residual add) where no norm follows (bf16 or fp32).
 //
 // Why: on the Llama-3 8B step (profiles/r5_llama8b_steady_steps.md) PyTorch's RoPE (chunk, neg,
 // cat, two multiplies, an add -- for q and k, forward and backward) and SwiGLU (split views, silu,
@@ -14,9 +15,14 @@
 // K15 swiglu: h = silu(g) u from the gate_up GEMM output [M, 2I] (g = columns 0..I-1, u = I..2I-1);
 //   the backward writes d[g | u] = [dh u silu'(g) | dh silu(g)] straight into the packed gradient
 //   the gate_up Linear's backward consumes.  silu via v_exp_f32 + v_rcp_f32.
+// K16 dropout_add: out = res + rp * m * x (or rp * m * x) on a [rows, H] view, H % 8 == 0, with the
+//   hidden-dropout mask of dropout.h generated in registers (no mask tensor; the backward, rp * m * g,
+//   is the same kernel without a residual).  One lane: two units of 8 consecutive columns (16-byte
+//   accesses, both units' loads issued before the Philox rounds), one Philox call per unit.
 // Reference: none (SURVEY §2.5 lists the Llama config's model zoo, not these kernels); numerics are
 // checked against fp32 PyTorch in tests/test_glue_gpu.py.
 #include "common.h"
+#include "dropout.h"
 
 namespace madnn {
 namespace glue {
@@ -127,6 +133,57 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const uint16_t* __restr
   }
 }
 
+// one unit = 8 consecutive columns of one row; a workgroup pass covers 512 consecutive units, two per lane
+template <int DT, bool RES>
+__global__ __launch_bounds__(256) void dropout_add_kernel(const void* __restrict__ x, const void* __restrict__ res,
+                                                          void* __restrict__ out, int64_t units, int per_row,
+                                                          const HiddenDrop dr) {
+  const DropRng rng = drop_rng(dr.seed, dr.offset);
+  for (int64_t base = (int64_t)blockIdx.x * 512; base < units; base += (int64_t)gridDim.x * 512) {
+    const int64_t brow = base / per_row;  // wave-uniform: the per-lane division below is 32-bit
+    const unsigned bunit = (unsigned)(base - brow * per_row);
+    int64_t u[2], row[2];
+    unsigned col[2];
+    float xv[2][8], rv[RES ? 2 : 1][8];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const unsigned lu = bunit + 256 * k + threadIdx.x;
+      u[k] = base + 256 * k + threadIdx.x;
+      row[k] = brow + lu / (unsigned)per_row;
+      col[k] = (lu % (unsigned)per_row) * 8;
+      if (u[k] < units) {
+        load8<DT>(x, u[k] * 8, xv[k]);
+        if constexpr (RES) load8<DT>(res, u[k] * 8, rv[k]);
+      }
+    }
+    uint32_t w[2][2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) hidden_words(rng, row[k], col[k] >> 4, (col[k] >> 3) & 1, w[k]);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (u[k] < units) {
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const bool keep = hidden_kept(w[k], j, dr.threshold);
+          if constexpr (RES) o[j] = keep ? fmaf(dr.rp, xv[k][j], rv[k][j]) : rv[k][j];
+          else o[j] = keep ? dr.rp * xv[k][j] : 0.f;
+        }
+        store8<DT>(out, u[k] * 8, o);
+      }
+    }
+  }
+}
+
+// The hidden-dropout mask itself (tests / debugging): out[r][c] = 1 iff (row0 + r, c) is kept
+__global__ __launch_bounds__(256) void hidden_dropout_mask_kernel(uint8_t* __restrict__ out, int64_t n, int H,
+                                                                  int64_t row0, uint32_t threshold, uint64_t seed,
+                                                                  uint64_t offset) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  out[idx] = hidden_keep(drop_rng(seed, offset), row0 + idx / H, idx % H, threshold) ? 1 : 0;
+}
+
 inline unsigned grid_for(int64_t units) {
   const int64_t g = (units + 255) / 256, cap = 8 * (int64_t)kNumCU;  // grid-stride beyond 8 WGs per CU
   return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
@@ -175,6 +232,37 @@ hipError_t madnn_swiglu_bwd(const void* dh, const void* gu, void* dgu, int64_t M
   if (units == 0) return hipSuccess;
   hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(units)), dim3(256), 0, st, static_cast<const uint16_t*>(dh),
                      static_cast<const uint16_t*>(gu), static_cast<uint16_t*>(dgu), units, I);
+  return hipGetLastError();
+}
+
+// out = res + rp * m * x (res == nullptr: rp * m * x) on [rows][H] contiguous, dt = kF32 / kBF16, H % 8 == 0
+hipError_t madnn_dropout_add(const void* x, const void* res, void* out, int64_t rows, int H, int dt, uint32_t threshold,
+                             uint64_t seed, uint64_t offset, hipStream_t st) {
+  if (H <= 0 || H % 8 || threshold < 1 || threshold > 256 || (dt != madnn::kF32 && dt != madnn::kBF16))
+    return hipErrorInvalidValue;
+  const int per_row = H / 8;
+  const int64_t units = rows * per_row;
+  if (units <= 0) return hipSuccess;
+  const madnn::HiddenDrop dr{seed, offset, threshold, 256.f / (float)threshold};
+  const unsigned grid = grid_for((units + 1) / 2);
+#define MADNN_K16(DT, RES) \
+  hipLaunchKernelGGL((dropout_add_kernel<DT, RES>), dim3(grid), dim3(256), 0, st, x, res, out, units, per_row, dr)
+  if (dt == madnn::kF32) {
+    if (res != nullptr) { MADNN_K16(madnn::kF32, true); } else { MADNN_K16(madnn::kF32, false); }
+  } else {
+    if (res != nullptr) { MADNN_K16(madnn::kBF16, true); } else { MADNN_K16(madnn::kBF16, false); }
+  }
+#undef MADNN_K16
+  return hipGetLastError();
+}
+
+hipError_t madnn_hidden_dropout_mask(uint8_t* out, int64_t rows, int H, int64_t row0, uint32_t threshold, uint64_t seed,
+                                     uint64_t offset, hipStream_t st) {
+  const int64_t n = rows * H;
+  if (n <= 0) return hipSuccess;
+  if (H <= 0 || (n + 255) / 256 > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hidden_dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, n, H, row0,
+                     threshold, seed, offset);
   return hipGetLastError();
 }
 

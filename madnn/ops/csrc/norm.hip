@@ -16,9 +16,15 @@
 //    chip-wide and non-deterministic).
 //  * The XCD swizzle is deliberately absent: there is no inter-block reuse on a
 //    row-wise op (cdna_hip_programming.md T1 "Transfer: 0% on LayerNorm").
+//  * DROP instantiations (hidden / residual dropout, residual mode only): the forward forms
+//    s = residual + rp * m * x in registers, the backward regenerates m and writes dh (the
+//    residual's gradient) and rp * m * dh (the dropped branch's) -- the mask (dropout.h) never
+//    exists in memory.  A lane's 8 columns are half a 16-column mask block: one Philox call per
+//    lane and chunk, half of its output used.
 #include <type_traits>
 
 #include "common.h"
+#include "dropout.h"
 
 namespace madnn {
 
@@ -80,11 +86,12 @@ struct Raw8 {
 // per row), and the next row's x (and residual) loads are issued before the current row's two
 // reductions, so every wave keeps a row of loads in flight while it reduces.  (Two rows in flight per
 // wave measured +0.05 % on the GPT-2 medium step, round 4: not kept.)
-template <int XDT, int WDT, int TPR, int NC>
+// DROP (res required): v = res + rp * m * x, exactly res where m drops.
+template <int XDT, int WDT, int TPR, int NC, bool DROP = false>
 __global__ __launch_bounds__(kNormThreads) void norm_fwd_kernel(
     const void* __restrict__ x, const void* __restrict__ res, const void* __restrict__ w, const void* __restrict__ b,
     void* __restrict__ y, void* __restrict__ sum_out, float* __restrict__ mean_out, float* __restrict__ rstd_out,
-    int64_t rows, int H, float eps, int rms) {
+    int64_t rows, int H, float eps, int rms, const HiddenDrop dr) {
   __shared__ __attribute__((aligned(16))) float red[kNormThreads / kWave];
   constexpr int RPB = kNormThreads / TPR;
   const int sub = threadIdx.x / TPR;
@@ -123,10 +130,13 @@ __global__ __launch_bounds__(kNormThreads) void norm_fwd_kernel(
     const int64_t row = row0 + sub;
     const bool live = row < rows;  // uniform per row group; all lanes still join the LDS reduction
     float v[NC][8];
+    [[maybe_unused]] float rr[DROP ? NC : 1][8];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       nx[c].unpack(v[c]);
-      if (res) {
+      if constexpr (DROP) {
+        nr[c].unpack(rr[c]);
+      } else if (res) {
         float r[8];
         nr[c].unpack(r);
 #pragma unroll
@@ -134,6 +144,19 @@ __global__ __launch_bounds__(kNormThreads) void norm_fwd_kernel(
       }
     }
     fetch(row + rstep);  // the next row flies under this row's reductions
+    if constexpr (DROP) {
+      if (live) {  // uniform per wave (a row group is whole waves)
+        const DropRng rng = drop_rng(dr.seed, dr.offset);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          uint32_t mw[2];
+          hidden_words(rng, row, (uint32_t)(c * TPR * 8 + t * 8) >> 4, t & 1, mw);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            v[c][j] = hidden_kept(mw, j, dr.threshold) ? fmaf(dr.rp, v[c][j], rr[c][j]) : rr[c][j];
+        }
+      }
+    }
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -190,11 +213,14 @@ __global__ __launch_bounds__(kNormThreads) void norm_fwd_kernel(
 // The weight is loaded once per lane (its columns never change across the grid-stride rows) and
 // the next row's x, dy, residual gradient and statistics are loaded before this row's reductions, so
 // their latency hides under them instead of following them.
-template <int XDT, int WDT, int TPR, int NC, bool CS>
+// DROP: dx takes dh (norm backward + dres: the residual's gradient), dx_drop = rp * m * dh (the
+// dropped branch's gradient, m regenerated), and the CS column sums are those of dx_drop.
+template <int XDT, int WDT, int TPR, int NC, bool CS, bool DROP = false>
 __global__ __launch_bounds__(kNormThreads) void norm_bwd_kernel(
     const void* __restrict__ dy, const void* __restrict__ x, const void* __restrict__ w,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in, const void* __restrict__ dres,
-    void* __restrict__ dx, float* __restrict__ partial, int64_t rows, int H, int rms, int has_bias) {
+    void* __restrict__ dx, float* __restrict__ partial, int64_t rows, int H, int rms, int has_bias,
+    void* __restrict__ dx_drop, const HiddenDrop dr) {
   constexpr int NS = CS ? 3 : 2;  // column sums per workgroup partial row
   __shared__ __attribute__((aligned(16))) float red[kNormThreads / kWave];
   extern __shared__ __attribute__((aligned(16))) float slab[];  // [RPB][NS][NC*TPR*8] when RPB > 1
@@ -308,6 +334,13 @@ __global__ __launch_bounds__(kNormThreads) void norm_bwd_kernel(
           for (int j = 0; j < 8; ++j) o[j] += rv[c][j];
         }
         store8<XDT>(dx, row * H + col, o);
+        if constexpr (DROP) {
+          uint32_t mw[2];
+          hidden_words(drop_rng(dr.seed, dr.offset), row, (uint32_t)col >> 4, t & 1, mw);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = hidden_kept(mw, j, dr.threshold) ? o[j] * dr.rp : 0.f;
+          store8<XDT>(dx_drop, row * H + col, o);
+        }
         if constexpr (CS) {
           // the sum of what is written (rounded to XDT, as the Linear's own column-sum pass would read it)
 #pragma unroll
@@ -463,7 +496,28 @@ hipError_t madnn_norm_fwd(const void* x, const void* res, const void* w, const v
       int64_t blocks = (rows + RPB - 1) / RPB;
       const int grid = blocks > g_norm_fwd_wg * kNumCU ? g_norm_fwd_wg * kNumCU : (int)blocks;
       hipLaunchKernelGGL((norm_fwd_kernel<XDT, WDT, TPR, NC>), dim3(grid), dim3(kNormThreads), 0, stream, x, res, w,
-                         b, y, sum_out, mean_out, rstd_out, rows, H, eps, rms);
+                         b, y, sum_out, mean_out, rstd_out, rows, H, eps, rms, HiddenDrop{});
+    });
+  });
+  return hipGetLastError();
+}
+
+// K3 DROP forward: sum_out = res + rp * m * x, y = norm(sum_out); threshold in 1..256 (see dropout.h)
+hipError_t madnn_norm_drop_fwd(const void* x, const void* res, const void* w, const void* b, void* y, void* sum_out,
+                               float* mean_out, float* rstd_out, int64_t rows, int H, float eps, int rms, int xdt,
+                               int wdt, uint32_t threshold, uint64_t seed, uint64_t offset, hipStream_t stream) {
+  using namespace madnn;
+  if (rows <= 0) return hipSuccess;
+  if (H % 8 != 0 || H > 16384 || threshold < 1 || threshold > 256 || res == nullptr || sum_out == nullptr)
+    return hipErrorInvalidValue;
+  const HiddenDrop dr{seed, offset, threshold, 256.f / (float)threshold};
+  MADNN_DISPATCH_XW(xdt, wdt, XDT, WDT, {
+    MADNN_NORM_CFG(H, TPR, NC, {
+      constexpr int RPB = kNormThreads / TPR;
+      int64_t blocks = (rows + RPB - 1) / RPB;
+      const int grid = blocks > g_norm_fwd_wg * kNumCU ? g_norm_fwd_wg * kNumCU : (int)blocks;
+      hipLaunchKernelGGL((norm_fwd_kernel<XDT, WDT, TPR, NC, true>), dim3(grid), dim3(kNormThreads), 0, stream, x,
+                         res, w, b, y, sum_out, mean_out, rstd_out, rows, H, eps, rms, dr);
     });
   });
   return hipGetLastError();
@@ -497,10 +551,42 @@ hipError_t madnn_norm_bwd(const void* dy, const void* x, const void* w, const fl
       const size_t lds = RPB > 1 ? (size_t)RPB * ns * NC * TPR * 8 * sizeof(float) : 0;
       if (dsum != nullptr) {
         hipLaunchKernelGGL((norm_bwd_kernel<XDT, WDT, TPR, NC, true>), dim3(G), dim3(kNormThreads), lds, stream,
-                           dy, x, w, mean_in, rstd_in, dres, dx, workspace, rows, H, rms, has_bias);
+                           dy, x, w, mean_in, rstd_in, dres, dx, workspace, rows, H, rms, has_bias, nullptr, HiddenDrop{});
       } else {
         hipLaunchKernelGGL((norm_bwd_kernel<XDT, WDT, TPR, NC, false>), dim3(G), dim3(kNormThreads), lds, stream,
-                           dy, x, w, mean_in, rstd_in, dres, dx, workspace, rows, H, rms, has_bias);
+                           dy, x, w, mean_in, rstd_in, dres, dx, workspace, rows, H, rms, has_bias, nullptr, HiddenDrop{});
+      }
+      MADNN_HIP_CHECK(hipGetLastError());
+      const int fgrid = ((dsum != nullptr ? 3 * H : (has_bias ? 2 * H : H)) + 31) / 32;
+      hipLaunchKernelGGL((norm_wgrad_finalize_kernel<WDT>), dim3(fgrid), dim3(32 * kWgSlices), 0, stream, workspace, G, H,
+                         has_bias, dw, dbias, ns, dsum, dsum_bf16);
+    });
+  });
+  return hipGetLastError();
+}
+
+// K3 DROP backward: dx = dh (the residual's gradient), dx_drop = rp * m * dh; dsum: column sums of dx_drop
+hipError_t madnn_norm_drop_bwd(const void* dy, const void* x, const void* w, const float* mean_in, const float* rstd_in,
+                               const void* dres, void* dx, void* dx_drop, void* dw, void* dbias, void* dsum,
+                               int dsum_bf16, float* workspace, int64_t rows, int H, int rms, int xdt, int wdt,
+                               uint32_t threshold, uint64_t seed, uint64_t offset, hipStream_t stream) {
+  using namespace madnn;
+  if (rows <= 0) return hipSuccess;
+  if (H % 8 != 0 || H > 16384 || threshold < 1 || threshold > 256 || dx_drop == nullptr) return hipErrorInvalidValue;
+  const HiddenDrop dr{seed, offset, threshold, 256.f / (float)threshold};
+  const int has_bias = dbias != nullptr;
+  const int G = (int)norm_bwd_groups(rows, H);
+  const int ns = dsum != nullptr ? 3 : 2;
+  MADNN_DISPATCH_XW(xdt, wdt, XDT, WDT, {
+    MADNN_NORM_CFG(H, TPR, NC, {
+      constexpr int RPB = kNormThreads / TPR;
+      const size_t lds = RPB > 1 ? (size_t)RPB * ns * NC * TPR * 8 * sizeof(float) : 0;
+      if (dsum != nullptr) {
+        hipLaunchKernelGGL((norm_bwd_kernel<XDT, WDT, TPR, NC, true, true>), dim3(G), dim3(kNormThreads), lds, stream,
+                           dy, x, w, mean_in, rstd_in, dres, dx, workspace, rows, H, rms, has_bias, dx_drop, dr);
+      } else {
+        hipLaunchKernelGGL((norm_bwd_kernel<XDT, WDT, TPR, NC, false, true>), dim3(G), dim3(kNormThreads), lds, stream,
+                           dy, x, w, mean_in, rstd_in, dres, dx, workspace, rows, H, rms, has_bias, dx_drop, dr);
       }
       MADNN_HIP_CHECK(hipGetLastError());
       const int fgrid = ((dsum != nullptr ? 3 * H : (has_bias ? 2 * H : H)) + 31) / 32;

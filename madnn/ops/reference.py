@@ -197,3 +197,36 @@ def attention_dropout_mask(B: int, H: int, S: int, p: float, seed: int, offset: 
     byts = (words[..., None] >> shifts) & np.uint64(0xFF)                   # [BH, qb, q & 3, kb, k & 3]
     keep = (byts < np.uint64(thr)).reshape(B, H, 4 * nb, 4 * nb)[:, :, :S, :S]
     return torch.from_numpy(np.ascontiguousarray(keep))
+
+
+def hidden_dropout_mask(rows: int, H: int, p: float, seed: int, offset: int, row0: int = 0) -> torch.Tensor:
+    """The keep mask of the hidden (residual) dropout of K3 / K16 for rows ``row0 .. row0 + rows - 1``
+    of a ``[*, H]`` activation, bool [rows, H], on the CPU in integer arithmetic: bit-identical to the
+    device function ``hidden_block`` of ``csrc/dropout.h``.  Philox4x32-10, key (seed lo, seed hi ^
+    offset hi) as K8's, counter (offset lo, row lo, row hi, col >> 4); the four output words are the 16
+    mask bytes of columns ``16 (col >> 4) .. + 15``: column ``col`` owns byte ``col & 3`` of word
+    ``(col >> 2) & 3`` and is kept iff it is ``< threshold``.  A pure function of (seed, offset, row,
+    col, threshold): ``H`` only bounds the columns returned."""
+    import numpy as np
+
+    thr = attention_dropout_threshold(p)
+    seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    m32 = np.uint64(0xFFFFFFFF)
+    nb = (H + 15) // 16
+    shape = (rows, nb)
+    r = np.arange(rows, dtype=np.uint64) + np.uint64(int(row0))
+    c0 = np.full(shape, offset & 0xFFFFFFFF, dtype=np.uint64)
+    c1 = np.broadcast_to((r & m32)[:, None], shape).copy()
+    c2 = np.broadcast_to((r >> np.uint64(32))[:, None], shape).copy()
+    c3 = np.broadcast_to(np.arange(nb, dtype=np.uint64)[None, :], shape).copy()
+    k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) ^ (offset >> 32)) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2   # 32 x 32 -> 64 bit, exact
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & m32,
+                          (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & m32)
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    words = np.stack([c0, c1, c2, c3], axis=2)                              # [rows, block, word]
+    shifts = (np.arange(4, dtype=np.uint64) * np.uint64(8))
+    byts = (words[..., None] >> shifts) & np.uint64(0xFF)                   # [rows, block, word, byte]
+    keep = (byts < np.uint64(thr)).reshape(rows, 16 * nb)[:, :H]
+    return torch.from_numpy(np.ascontiguousarray(keep))
