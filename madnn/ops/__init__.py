@@ -895,13 +895,16 @@ _K9_DGRAD = os.environ.get("MADNN_K9_DGRAD", "narrow")  # "wide" | "narrow" (A/B
 # A/B switch: K9's forward / data-grad main loop.  Off: register-staged; on: the LDS-DMA ring (weight slice
 # LDS-resident) on the shapes whose slice fits its 32 KiB (conv.hip use_ring); the others stay register-staged.
 K9_RING = os.environ.get("MADNN_K9_RING", "1") != "0"
+# A/B switch: the deep 1x1 forwards (Cin >= 256, Cout >= Cin, 256-multiples of pixels and Cout) and the deep plain
+# data grad run on K12P, the forwards with the BatchNorm statistics in its epilogue (conv.hip use_deep).  Off: K9.
+K9_DEEP = os.environ.get("MADNN_K9_DEEP", "1") != "0"
 _K9_TUNE = []
 
 
 def conv1x1_tune(key: int, value: int = -1) -> int:
     """K9's native tunables (``madnn_conv1x1_tune``): key 0 the forward / data-grad persistent grid target,
-    1 the weight-grad workgroups, 2 the XCD remap, 3 the ring switch.  Sets ``value`` (>= 0) and returns the
-    previous one; ``value < 0`` only reads."""
+    1 the weight-grad workgroups, 2 the XCD remap, 3 the ring switch, 4 the deep-shapes-on-K12P switch.  Sets
+    ``value`` (>= 0) and returns the previous one; ``value < 0`` only reads."""
     _need_native("conv1x1_tune")
     if not _K9_TUNE:
         import ctypes
@@ -911,8 +914,10 @@ def conv1x1_tune(key: int, value: int = -1) -> int:
 
 
 def _k9():
-    """``torch.ops.madnn`` for a K9 forward / data-grad launch, the native ring switch set to ``K9_RING``."""
+    """``torch.ops.madnn`` for a K9 forward / data-grad launch, the native ring and deep switches set to
+    ``K9_RING`` / ``K9_DEEP``."""
     conv1x1_tune(3, 1 if K9_RING else 0)
+    conv1x1_tune(4, 1 if K9_DEEP else 0)
     return torch.ops.madnn
 
 

@@ -46,6 +46,16 @@
 
 #include "mfma.h"
 
+// K12P (gemmp.hip): the deep forwards and the deep plain data grad run there (use_deep)
+extern "C" {
+int madnn_gemmp_supported(int64_t I, int64_t J, int64_t K, int has_bias);
+int madnn_conv1x1_fwd_p_rows(int64_t M, int64_t cout);
+hipError_t madnn_conv1x1_fwd_p(const void* x, const void* w, void* y, float* stats, int64_t M, int64_t cin,
+                               int64_t cout, hipStream_t s);
+hipError_t madnn_linear_dgrad_p(const void* dy, const void* w, const void* pre, void* dx, float* colsum, int64_t M,
+                                int64_t N, int64_t K, int gelu_kind, hipStream_t s);
+}
+
 namespace madnn {
 namespace conv {
 
@@ -63,6 +73,11 @@ struct Tune {
   int ring = ring_default();  // store-mode main loop: 0 register-staged, 1 LDS-DMA ring where it applies (use_ring)
   static int ring_default() {
     const char* e = getenv("MADNN_K9_RING");
+    return e != nullptr && *e != 0 ? atoi(e) : 1;
+  }
+  int deep = deep_default();  // deep forwards / the deep plain data grad on K12P (gemmp.hip) where use_deep says so
+  static int deep_default() {
+    const char* e = getenv("MADNN_K9_DEEP");
     return e != nullptr && *e != 0 ? atoi(e) : 1;
   }
 };
@@ -694,6 +709,23 @@ inline bool use_ring(bool a_col, int bi, int64_t K) {
   return bi == 128 ? nk <= 2 : (nk >= 2 && nk <= 4);
 }
 
+// Does the forward (or, with dgrad, the plain data grad: no residual, no BN sums) run on K12P, the persistent
+// 256x256-tile 8-wave GEMM of gemmp.hip, instead of K9?  Where K12P takes the shape (M and the output channels
+// multiples of 256, the reduction a multiple of 64) and both channel counts are deep: Cin >= 256 with Cout >= Cin.
+// Measured: the five such channel pairs of the ResNet-50 step (256 -> 512, 256 -> 1024, 512 -> 1024, 512 -> 2048,
+// 1024 -> 2048) and the 256 -> 512 data grad, at M = 25088 .. 1605632, each 1.2-2.0x faster than K9 by more than
+// both arms' spreads at 2048 and at 512 images (profiles/r14_k12p_plain_vs_k9.json); K9's four waves per workgroup
+// cannot keep the MFMAs fed there (docs/PERF.md rounds 12, 14).  With the BatchNorm consumer counted
+// (profiles/r14_k12p_deep_kernel_ab_b512.json) 256 -> 1024 at M = 100352 is even, not faster: its M / 64 partial
+// rows cross the consumer's prereduce threshold.  Not measured, and on K12P by extension only: other pairs the
+// rule admits (square ones such as 256 -> 256, 512 -> 512) and small M, where K12P has (M / 256) * (Cout / 256)
+// tiles for 256 CUs.  The rule has no bound on M because the small shapes of tests/test_conv1x1_deep_gpu.py must
+// reach the kernel.  Shallower or contracting shapes were not measured and stay on K9.
+inline bool use_deep(int64_t M, int64_t cin, int64_t cout, bool dgrad = false) {
+  if (tune().deep <= 0 || cin < 256 || cout < cin) return false;
+  return (dgrad ? madnn_gemmp_supported(cin, M, cout, 0) : madnn_gemmp_supported(cout, M, cin, 0)) != 0;
+}
+
 // i-tile width of the forward: 128 where Cout allows, except that with the ring on K = 192 / 256 take 64-wide
 // tiles, whose weight slice fits the ring's 32 KiB (measured faster than 128-wide register-staged tiles:
 // docs/PERF.md round 12).  The plan, and with it the number of partial rows, follows the width.
@@ -1045,13 +1077,14 @@ using namespace madnn::conv;
 
 extern "C" {
 
-// key 0: forward/dgrad grid target, 1: weight-grad workgroups, 2: XCD remap (0/1), 3: ring main loop (0/1);
-// returns the old value (value < 0: query only)
+// key 0: forward/dgrad grid target, 1: weight-grad workgroups, 2: XCD remap (0/1), 3: ring main loop (0/1),
+// 4: deep forwards / plain data grad on K12P (0/1); returns the old value (value < 0: query only)
 int madnn_conv1x1_tune(int key, int value) {
   int* f = key == 0   ? &tune().fwd_wg
            : key == 1 ? &tune().wgrad_wg
            : key == 2 ? &tune().xcd
            : key == 3 ? &tune().ring
+           : key == 4 ? &tune().deep
                       : nullptr;
   if (f == nullptr) return -1;
   const int old = *f;
@@ -1066,6 +1099,7 @@ int madnn_conv1x1_supported(int64_t cin, int64_t cout) {
 // partial-statistics rows the forward writes ([rows][2][cout] fp32)
 int madnn_conv1x1_stat_rows(int64_t M, int64_t cin, int64_t cout) {
   if (!madnn_conv1x1_supported(cin, cout) || M <= 0) return 0;
+  if (use_deep(M, cin, cout)) return madnn_conv1x1_fwd_p_rows(M, cout);
   GemmArgs p{};
   plan_persistent(p, M, fwd_bi(cin, cout), cout, cin);
   return p.j_groups;
@@ -1083,6 +1117,7 @@ hipError_t madnn_conv1x1_fwd(const void* x, const void* w, void* y, float* stats
                              int64_t cout, hipStream_t s) {
   if (!madnn_conv1x1_supported(cin, cout)) return hipErrorInvalidValue;
   if (M <= 0) return hipSuccess;
+  if (use_deep(M, cin, cout)) return madnn_conv1x1_fwd_p(x, w, y, stats, M, cin, cout, s);
   GemmArgs p{};
   p.a = static_cast<const uint16_t*>(w);
   p.lda = cin;
@@ -1118,6 +1153,8 @@ hipError_t madnn_conv1x1_dgrad(const void* dy, const void* w, void* dx, const vo
                                hipStream_t s, const unsigned char* resmask) {
   if (!madnn_conv1x1_supported(cin, cout)) return hipErrorInvalidValue;
   if (M <= 0) return hipSuccess;
+  if (res == nullptr && bny == nullptr && use_deep(M, cin, cout, true))
+    return madnn_linear_dgrad_p(dy, w, nullptr, dx, nullptr, M, cout, cin, 1, s);
   GemmArgs p{};
   p.a = static_cast<const uint16_t*>(w);  // A[i = ci][k = co] = W[co][ci]: column memory
   p.lda = cin;

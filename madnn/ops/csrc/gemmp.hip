@@ -19,7 +19,11 @@
 //     outputs of one row: one 16-B store per pair (a wave instruction writes 16 rows x 64 B);
 //   * kPlain: (acc + bias) -> bf16;  kGelu: h = bf16(acc + bias) stored as the pre-activation,
 //     out = bf16(gelu(h));  kDGelu: dh = bf16(bf16(acc) * gelu'(pre)), plus fp32 column sums of
-//     dh (the c_fc bias gradient) as per-wave partial rows [j_tiles * 4][I] for a finalize pass.
+//     dh (the c_fc bias gradient) as per-wave partial rows [j_tiles * 4][I] for a finalize pass;
+//     kStats: bf16(acc) stored as kPlain does without a bias, plus per column the fp32 sum and sum of
+//     squares of those bf16-rounded values over the wave's 64 rows, as partial rows
+//     [j_tiles * 4][2][I] -- the BatchNorm partial-statistics layout of K9's forward (conv.hip header),
+//     which bn.hip's finalize takes in place of its own statistics pass (the deep 1x1 convolutions).
 //   The formulas and roundings are the unfused passes' own (gelu.h): fused == unfused.
 // vmcnt across an epilogue: loads, stores and LDS-DMA retire in issue order on one counter, so the
 // epilogue first issues the DMA that the next K tile's Q0/Q1 would have issued (the A halves of
@@ -38,14 +42,15 @@ namespace gemmp {
 using namespace mf;
 using namespace k12;
 
-enum Epi : int { kPlain = 0, kGelu = 1, kDGelu = 2 };
+enum Epi : int { kPlain = 0, kGelu = 1, kDGelu = 2, kStats = 3 };
 
 constexpr int kBiasMax = 8192;  // fp32 bias entries staged in LDS beside the 128 KiB of stages
 
-// VMEM stores per wave per epilogue: 16 output pairs (+16 pre-activation / +4 column-sum dwords)
+// VMEM stores per wave per epilogue: 16 output pairs (+16 pre-activation / +4 column-sum dwords /
+// +8 statistics dwords: a sum and a sum of squares per pair)
 template <int EPI>
 constexpr int store_count() {
-  return EPI == kGelu ? 32 : EPI == kDGelu ? 20 : 16;
+  return EPI == kGelu ? 32 : EPI == kDGelu ? 20 : EPI == kStats ? 24 : 16;
 }
 
 struct PArgs {
@@ -55,7 +60,7 @@ struct PArgs {
   uint16_t* aux;         // kGelu: pre-activation store, same layout
   const uint16_t* pre;   // kDGelu: pre-activation read, same layout
   const void* bias;      // kPlain / kGelu: [I] fp32 (bias_f32) or bf16, or null
-  float* colsum;         // kDGelu: [j_tiles * 4][I] fp32 partial column sums
+  float* colsum;         // kDGelu: [j_tiles * 4][I] fp32 partial column sums; kStats: [j_tiles * 4][2][I]
   int64_t lda, ldb, ldo;
   int64_t I, J, K;
   int i_tiles, j_tiles, nk, ntile;
@@ -74,6 +79,22 @@ __device__ __forceinline__ u32x4 swap_pairs(unsigned x0, unsigned x1, unsigned y
   const auto d0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
   const auto d1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
   return u32x4{d0[0], d1[0], d0[1], d1[1]};
+}
+
+// Column sums over a wave's 64 rows: each lane holds 8 consecutive outputs' sums over its own rows,
+// and the 16 lanes of a lane row hold 16 different rows.  A reduce-scatter over lane bits 3, 2, 1,
+// then a sum over bit 0 -- the lane ends with the total of output 4 b3 + 2 b2 + b1 of its 8 (lanes
+// 2k, 2k+1 agree).  Fixed order: deterministic.
+__device__ __forceinline__ float colsum64(const float (&cs)[8], int el16) {
+  const bool b3 = el16 & 8, b2 = el16 & 4, b1 = el16 & 2;
+  float r4[4], r2[2];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r4[k] = (b3 ? cs[4 + k] : cs[k]) + __shfl_xor(b3 ? cs[k] : cs[4 + k], 8);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) r2[k] = (b2 ? r4[2 + k] : r4[k]) + __shfl_xor(b2 ? r4[k] : r4[2 + k], 4);
+  float v = (b1 ? r2[1] : r2[0]) + __shfl_xor(b1 ? r2[0] : r2[1], 2);
+  v += __shfl_xor(v, 1);
+  return v;
 }
 
 template <bool A_COL, bool B_COL, int EPI, int GK = kGeluTanh>
@@ -96,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
   const int nk = p.nk;
   const int total = 4 * ntiles * nk;  // half-tiles in this workgroup's DMA stream
 
-  const bool has_bias = EPI != kDGelu && p.bias != nullptr;
+  const bool has_bias = (EPI == kPlain || EPI == kGelu) && p.bias != nullptr;
   if (has_bias) {  // before any DMA: ordinary loads + one plain barrier
     for (int i = tid; i < p.I; i += kThreads)
       sbias[i] = p.bias_f32 ? static_cast<const float*>(p.bias)[i]
@@ -342,20 +363,7 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
               ov[mm][b][k] = pack2(v0, v1);
             }
           }
-          // column sums over this wave's 64 rows (the 16 lanes of a lane row hold 16 different
-          // rows): a reduce-scatter over lane bits 3, 2, 1, then a sum over bit 0 -- this lane
-          // ends with the total of output 4 b3 + 2 b2 + b1 of its 8 (lanes 2k, 2k+1 agree)
-          const bool b3 = el16 & 8, b2 = el16 & 4, b1 = el16 & 2;
-          float r4[4], r2[2];
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            r4[k] = (b3 ? cs[4 + k] : cs[k]) + __shfl_xor(b3 ? cs[k] : cs[4 + k], 8);
-#pragma unroll
-          for (int k = 0; k < 2; ++k)
-            r2[k] = (b2 ? r4[2 + k] : r4[k]) + __shfl_xor(b2 ? r4[k] : r4[2 + k], 4);
-          float v = (b1 ? r2[1] : r2[0]) + __shfl_xor(b1 ? r2[0] : r2[1], 2);
-          v += __shfl_xor(v, 1);
-          cv[mm] = v;
+          cv[mm] = colsum64(cs, el16);  // over this wave's 64 rows
         }
       };
       auto store_half = [&](int h) {
@@ -377,6 +385,36 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
       __builtin_amdgcn_sched_barrier(0);
       compute_half(1);
       store_half(1);
+    } else if constexpr (EPI == kStats) {
+      // per pair: 4 output stores, then the pair's two statistics dwords (even lanes; the instruction is
+      // issued by every wave for every tile, so the count S is exact) -- no loads, no LDS
+      float* srow = p.colsum + ((j0 / kT) * 4 + wc) * 2 * p.I + ib + io;
+      const int cidx = 4 * ((el16 >> 3) & 1) + 2 * ((el16 >> 2) & 1) + ((el16 >> 1) & 1);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        float cs[8], cq[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) cs[e] = cq[e] = 0.f;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const f32x4 X = ac4[2 * m][b], Y = ac4[2 * m + 1][b];
+          const u32x4 h = swap_pairs(pack2(X[0], X[1]), pack2(X[2], X[3]), pack2(Y[0], Y[1]), pack2(Y[2], Y[3]));
+          *reinterpret_cast<u32x4*>(p.out + (jb + 16 * b) * p.ldo + ib + 32 * m + io) = h;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float v0 = lo16(h[k]), v1 = hi16(h[k]);  // the stored (bf16-rounded) values
+            cs[2 * k] += v0;
+            cs[2 * k + 1] += v1;
+            cq[2 * k] += v0 * v0;
+            cq[2 * k + 1] += v1 * v1;
+          }
+        }
+        const float vs = colsum64(cs, el16), vq = colsum64(cq, el16);
+        if ((el16 & 1) == 0) {
+          srow[32 * m + cidx] = vs;
+          srow[p.I + 32 * m + cidx] = vq;
+        }
+      }
     } else {
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -516,6 +554,32 @@ hipError_t madnn_linear_fwd_p(const void* x, const void* w, const void* bias, in
   return act == kGeluTanh ? launch<false, kGelu, kGeluTanh>(p, s)
          : act == kGeluErf ? launch<false, kGelu, kGeluErf>(p, s)
                            : launch<false, kPlain>(p, s);
+}
+
+// The deep 1x1 convolution forward on NHWC rows, Y[m][co] = X[m][ci] W[co][ci] (no bias), with the
+// following BatchNorm's partial statistics: stats (or null: the plain kernel) gets
+// [madnn_conv1x1_fwd_p_rows][2][cout] fp32, one (sum, sum of squares) row pair per wave and tile
+// over the bf16-rounded outputs -- what K9's forward writes per workgroup (conv.hip header)
+int madnn_conv1x1_fwd_p_rows(int64_t M, int64_t cout) {
+  (void)cout;
+  return (int)(M / kT * 4);
+}
+
+hipError_t madnn_conv1x1_fwd_p(const void* x, const void* w, void* y, float* stats, int64_t M, int64_t cin,
+                               int64_t cout, hipStream_t s) {
+  if (!madnn_gemmp_supported(cout, M, cin, 0)) return hipErrorInvalidValue;
+  PArgs p{};
+  p.a = static_cast<const uint16_t*>(w);
+  p.lda = cin;
+  p.b = static_cast<const uint16_t*>(x);
+  p.ldb = cin;
+  p.out = static_cast<uint16_t*>(y);
+  p.ldo = cout;
+  p.colsum = stats;
+  p.I = cout;
+  p.J = M;
+  p.K = cin;
+  return stats != nullptr ? launch<false, kStats>(p, s) : launch<false, kPlain>(p, s);
 }
 
 // dX[m][k] = dY[m][n] W[n][k]; with pre: dX = that * gelu'(pre) (gelu_kind 1 tanh / 2 erf) and the
