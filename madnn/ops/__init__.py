@@ -8,6 +8,7 @@ which is also the numerics oracle for the kernel tests.
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 from pathlib import Path
@@ -750,13 +751,20 @@ def _dropout_args(t: torch.Tensor, dropout_p: float, rng, gen=None) -> tuple:
     return float(dropout_p), s64(seed), s64(offset)
 
 
+def _attn_scale_ok(scale: float) -> bool:
+    """The softmax scales K8 takes: finite and positive (``attn_args`` in binding.cpp checks the same)."""
+    return math.isfinite(scale) and scale > 0
+
+
 def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dropout_p: float = 0.0, rng=None):
     """Scaled-dot-product attention on [B, S, heads, D] tensors (GQA when k/v have fewer heads).
     Returns [B, S, H, D].  HIP bf16 inputs run K8; anything else runs SDPA.  ``dropout_p`` drops
     attention probabilities (K8: in-kernel mask, see :func:`reference.attention_dropout_mask`);
-    ``rng = (seed, offset)`` pins K8's mask, by default it is drawn from torch's device generator."""
+    ``rng = (seed, offset)`` pins K8's mask, by default it is drawn from torch's device generator.
+    K8 takes a finite positive ``scale`` only (its kernels refuse any other: they mask with
+    infinities before scaling); a zero, negative or non-finite scale runs :func:`reference.attention`."""
     scale = scale if scale is not None else q.size(-1) ** -0.5
-    if attention_supported(q, q.size(-1), dropout_p):
+    if attention_supported(q, q.size(-1), dropout_p) and _attn_scale_ok(scale):
         _need_native("attention")
         return _AttnFn.apply(q, k, v, causal, scale, *_dropout_args(q, dropout_p, rng))
     return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p)
@@ -765,10 +773,11 @@ def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dr
 def attention_qkvpacked(qkv, heads: int, kv_heads: int, *, causal: bool = True, scale: Optional[float] = None,
                         dropout_p: float = 0.0, rng=None):
     """Attention straight from a packed projection ``qkv`` [B, S, heads + 2*kv_heads, D]
-    (``dropout_p`` / ``rng`` as in :func:`attention`)."""
+    (``dropout_p`` / ``rng`` as in :func:`attention`; a ``scale`` that is not finite and positive runs
+    :func:`reference.attention`, as there)."""
     d = qkv.size(-1)
     scale = scale if scale is not None else d ** -0.5
-    if attention_supported(qkv, d, dropout_p) and qkv.is_contiguous():
+    if attention_supported(qkv, d, dropout_p) and qkv.is_contiguous() and _attn_scale_ok(scale):
         _need_native("attention")
         return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_dropout_args(qkv, dropout_p, rng))
     q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)

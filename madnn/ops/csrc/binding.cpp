@@ -11,6 +11,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <vector>
 
 #include "attn.h"
@@ -1517,6 +1518,9 @@ MadnnAttnArgs attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tens
   TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0) && k.size(1) == q.size(1), "attention: k/v shape");
   TORCH_CHECK(q.size(2) % k.size(2) == 0, "attention: query heads must be a multiple of kv heads");
   TORCH_CHECK(q.size(1) < (1ll << 30) && q.size(0) * q.size(2) < (1ll << 30), "attention: problem too large");
+  // the kernels mask with +-inf BEFORE the multiply by scale_log2 (register-staged dK/dV) or on operands
+  // prescaled by -scale_log2: a scale <= 0 turns a masked score into +inf or NaN
+  TORCH_CHECK(std::isfinite(scale) && scale > 0, "attention: scale must be finite and positive, got ", scale);
   MadnnAttnArgs a{};
   a.q = reinterpret_cast<const uint16_t*>(q.data_ptr());
   a.k = reinterpret_cast<const uint16_t*>(k.data_ptr());

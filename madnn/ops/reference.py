@@ -145,10 +145,22 @@ def cross_entropy(logits, targets, *, shift=False, vocab=None, ignore_index=-100
 
 def attention(q, k, v, *, causal=True, scale=None, dropout_p=0.0):
     """[B, S, H, D] / [B, S, Hkv, D] -> [B, S, H, D] via SDPA (fp32 oracle when given fp32).
-    ``dropout_p`` is SDPA's own dropout (torch's mask, not K8's)."""
+    ``dropout_p`` is SDPA's own dropout (torch's mask, not K8's).  A ``scale`` that is not finite and
+    positive is computed from plain ops in fp32 instead: SDPA's math path takes the square root of
+    the scale, and its fused bf16 backward on the device returned NaN gradients for a negative one."""
     import torch.nn.functional as F
 
     h, hkv = q.size(2), k.size(2)
+    if scale is not None and not (math.isfinite(scale) and scale > 0):
+        qt, kt, vt = (t.transpose(1, 2).float() for t in (q, k, v))
+        if h != hkv:
+            kt, vt = kt.repeat_interleave(h // hkv, dim=1), vt.repeat_interleave(h // hkv, dim=1)
+        s = (qt @ kt.transpose(-1, -2)) * scale
+        if causal:
+            n = s.size(-1)
+            s = s.masked_fill(~torch.ones(n, n, dtype=torch.bool, device=s.device).tril(), float("-inf"))
+        p = F.dropout(torch.softmax(s, dim=-1), dropout_p)
+        return (p @ vt).to(q.dtype).transpose(1, 2).contiguous()
     o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), dropout_p=dropout_p,
                                        is_causal=causal, scale=scale, enable_gqa=h != hkv)
     return o.transpose(1, 2).contiguous()

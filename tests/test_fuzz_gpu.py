@@ -99,3 +99,16 @@ def test_fuzz_k13_conv3x3(cuda, nb, h, w, ci, co):
     wr = torch.zeros(co, ci, 3, 3, device=cuda, requires_grad=True)
     F.conv2d(xr, wr, None, 1, 1).backward(dy.float())
     torch.testing.assert_close(dw, wr.grad, atol=3e-3 * (nb * h * w) ** 0.5, rtol=1e-3)
+
+
+@FUZZ
+@given(B=st.integers(1, 3), S=st.integers(1, 300), HKV=st.integers(1, 3), G=st.sampled_from([1, 2, 3, 4]),
+       D=st.sampled_from([64, 128]), causal=st.booleans(), scale=st.sampled_from([None, 0.3, "1/D"]),
+       p=st.sampled_from([0.0, 0.1]))
+def test_fuzz_k8_attention(cuda, B, S, HKV, G, D, causal, scale, p):
+    """K8 forward plus all three gradients against fp32 SDPA (the host-mask reference when p > 0),
+    under the bounds of test_attention_edges_gpu.check_case: 1.5e-2 / 3e-2 at scale 0.3, else 1e-2 /
+    2e-2; o elementwise (atol = rtol = 3e-2) instead of its norm at S < 8."""
+    from test_attention_edges_gpu import check_case
+
+    check_case(cuda, B, S, HKV * G, HKV, D, causal, 1.0 / D if scale == "1/D" else scale, p=p, fuzz=True)
