@@ -55,88 +55,22 @@
 #include <type_traits>
 
 #include "attn.h"
-#include "common.h"
 #include "dropout.h"
+#include "mfma.h"
 
 namespace madnn {
 namespace attn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using namespace mf;
 
 constexpr int kThreads = 256;  // 4 waves
 constexpr int kRowsWG = 128;   // query rows per workgroup (fwd, dQ) / key rows (dK/dV)
 constexpr int kTile = 64;      // keys per tile (fwd, dQ) / queries per tile (dK/dV)
 constexpr float kNegBig = -1.0e30f;
 
-__device__ __forceinline__ f32x16 mfma(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // v_exp_f32 directly (exp2f adds denormal range reduction: 4 more VALU per element; a
 // softmax weight below 2^-126 is 0 either way)
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
-// Byte offset of 16-B chunk `ch` of row `row` in a [64][D] bf16 LDS tile.
-// D = 64 (128-B rows, 2 rows per 256-B bank row): ch ^ f(row), f = ((row>>1)&1)<<2 | (row>>2)&3.
-//   ds_read_b128 groups {0-3,12-15,20-27} / {4-11,16-19,28-31} (row = lane): the 8 even and the 8
-//   odd rows of each group get 8 distinct f -> 16 distinct 16-B slots.  Transposed read (rows
-//   4n..4n+3, an aligned 4-chunk group per 32-lane half): rows 4n, 4n+2 differ in f bit 2, rows
-//   4n+1, 4n+3 sit in the other half of the bank row -> 16 distinct slots.
-// D = 128 (256-B rows): the dual-use image (b) of cdna_hip_programming.md T10.
-template <int D>
-__device__ __forceinline__ int swz(int row, int ch) {
-  if constexpr (D == 64) {
-    return row * 128 + 16 * (ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3)));
-  } else {
-    return row * 256 + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-  }
-}
-
-// MFMA operand with the head dim as k: 8 bf16 of row `row`, chunk `ch` (ds_read_b128).
-template <int D>
-__device__ __forceinline__ bf16x8 lds_row(const uint16_t* tile, int row, int ch) {
-  return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(tile) + swz<D>(row, ch));
-}
-
-// MFMA operand with the tile's ROW index as k (two ds_read_b64_tr_b16): element j of lane half h
-// is tile[r0 + 8*(j>>2) + 4h + (j&3)][c0 + (lane&31)] -- the k order in which an f32x16
-// accumulator's registers 8s..8s+7 serve as the other operand (pack_acc).
-template <int D>
-__device__ __forceinline__ bf16x8 lds_tr(const uint16_t* tile, int r0, int c0, int lane) {
-  const int g = lane >> 4, i = lane & 15;
-  const int col = c0 + 16 * (g & 1) + 4 * (i & 3);
-  const int row = r0 + 4 * (g >> 1) + (i >> 2);
-  const char* base = reinterpret_cast<const char*>(tile);
-  const int sub = 8 * ((col >> 2) & 1);
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + swz<D>(row, col >> 3) + sub));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + swz<D>(row + 8, col >> 3) + sub));
-  const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
-}
-
-// registers 8s..8s+7 of an accumulator -> bf16 operand fragment (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ bf16x8 pack_acc(const f32x16& x, int s) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = static_cast<__bf16>(x[8 * s + j]);
-  return r;
-}
-
-// accumulator register r of lane half h -> row within the 32-row block
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // 8 bf16 scaled by k and rounded back to bf16: the exp2-domain operand prescale (row constants as
 // the initial accumulator, cdna_hip_programming.md 'Attention backward'): with Q (or K) prescaled by
@@ -207,21 +141,12 @@ struct TileStage {
 // Workgroup -> (sequence block, batch, head): consecutive logical ids on one XCD
 // (bijective remap, cdna_hip_programming.md "XCD swizzle must be bijective").
 __device__ __forceinline__ void map_block(int nblk, int heads, bool heavy_last, int& blk, int& b, int& h) {
-  const int nwg = gridDim.x;
-  const int id = blockIdx.x;
-  const int xcd = id % 8, q8 = nwg / 8, r8 = nwg % 8;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + id / 8;
+  const int wg = xcd_group_id(blockIdx.x, gridDim.x);
   const int bh = wg / nblk;
   blk = wg % nblk;
   if (heavy_last) blk = nblk - 1 - blk;  // causal: the longest query blocks start first
   b = bh / heads;
   h = bh % heads;
-}
-
-__device__ __forceinline__ void store4_bf16(uint16_t* p, float a, float b, float c, float d) {
-  const unsigned lo = (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
-  const unsigned hi = (unsigned)f32_to_bf16(c) | ((unsigned)f32_to_bf16(d) << 16);
-  *reinterpret_cast<u32x2*>(p) = u32x2{lo, hi};
 }
 
 // ------------------------------------------------------------------ dropout mask
@@ -405,7 +330,7 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
         for (int s = 0; s < 2; ++s) {
           const bf16x8 pf = pack_acc(sc[kb], s);
 #pragma unroll
-          for (int d = 0; d < DB; ++d) o[d] = mfma(lds_tr<D>(sV[cur], kb * 32 + 16 * s, d * 32, lane), pf, o[d]);
+          for (int d = 0; d < DB; ++d) o[d] = mfma(lds_col_acc<D>(sV[cur], kb * 32 + 16 * s, d * 32, lane), pf, o[d]);
         }
       }
     }
@@ -535,7 +460,7 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
         for (int s = 0; s < 2; ++s) {
           const bf16x8 sf = pack_acc(sc, s);
 #pragma unroll
-          for (int d = 0; d < DB; ++d) dq[d] = mfma(lds_tr<D>(sK[cur], kb * 32 + 16 * s, d * 32, lane), sf, dq[d]);
+          for (int d = 0; d < DB; ++d) dq[d] = mfma(lds_col_acc<D>(sK[cur], kb * 32 + 16 * s, d * 32, lane), sf, dq[d]);
         }
       }
     } else if (!CAUSAL || k0 <= q0w + 31) {
@@ -586,7 +511,7 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
         for (int s = 0; s < 2; ++s) {
           const bf16x8 sf = pack_acc(sc[kb], s);
 #pragma unroll
-          for (int d = 0; d < DB; ++d) dq[d] = mfma(lds_tr<D>(sK[cur], kb * 32 + 16 * s, d * 32, lane), sf, dq[d]);
+          for (int d = 0; d < DB; ++d) dq[d] = mfma(lds_col_acc<D>(sK[cur], kb * 32 + 16 * s, d * 32, lane), sf, dq[d]);
         }
       }
     }
@@ -679,7 +604,7 @@ __device__ __forceinline__ void dma_stats(const float* arr, float* dst) {
 __device__ __forceinline__ void raw_barrier() {
   // an LDS-DMA is a pending LDS write on the VM counter: __syncthreads() would drain it (vmcnt(0))
   __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkmcnt0();
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 }
@@ -753,9 +678,9 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_dma_kernel(const Madnn
   // per-wave DMA instructions per tile (Q 2 + dO 2, + 1 statistics row on waves 0 / 1)
   auto wait_all_but_one_tile = [&]() {
     if (wave < 2) {
-      asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      wait_vmcnt<5>();
     } else {
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      wait_vmcnt<4>();
     }
   };
   if (total > 0) issue(0);
@@ -763,7 +688,7 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_dma_kernel(const Madnn
     issue(1);
     wait_all_but_one_tile();
   } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
   }
   raw_barrier();
   int it = 0, cur_t = 0;
@@ -816,8 +741,8 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_dma_kernel(const Madnn
           const bf16x8 sf = pack_acc(dp[qb], s);
 #pragma unroll
           for (int d = 0; d < DB; ++d) {
-            dv[d] = mfma(pf, lds_tr<D>(to, qb * 32 + 16 * s, d * 32, lane), dv[d]);
-            dk[d] = mfma(sf, lds_tr<D>(tq, qb * 32 + 16 * s, d * 32, lane), dk[d]);
+            dv[d] = mfma(pf, lds_col_acc<D>(to, qb * 32 + 16 * s, d * 32, lane), dv[d]);
+            dk[d] = mfma(sf, lds_col_acc<D>(tq, qb * 32 + 16 * s, d * 32, lane), dk[d]);
           }
         }
       }
@@ -827,7 +752,7 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_dkdv_dma_kernel(const Madnn
     if (it + 2 < total) {
       wait_all_but_one_tile();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
     raw_barrier();
     ++it;
@@ -904,9 +829,9 @@ struct KVRing64 {
     if (ntiles > 0) issue(0, 0);
     if (ntiles > 1) {
       issue(1, 1);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      wait_vmcnt<4>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
     raw_barrier();
   }
@@ -915,9 +840,9 @@ struct KVRing64 {
   }
   __device__ __forceinline__ void tile_end(int t) const {
     if (t + 2 < ntiles) {
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      wait_vmcnt<4>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
     raw_barrier();
   }
@@ -986,7 +911,7 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_dma_kernel(const MadnnAttnA
         for (int s = 0; s < 2; ++s) {
           const bf16x8 pf = pack_acc(sc[kb], s);
 #pragma unroll
-          for (int d = 0; d < DB; ++d) o[d] = mfma(lds_tr<D>(tv, kb * 32 + 16 * s, d * 32, lane), pf, o[d]);
+          for (int d = 0; d < DB; ++d) o[d] = mfma(lds_col_acc<D>(tv, kb * 32 + 16 * s, d * 32, lane), pf, o[d]);
         }
       }
     }
@@ -1188,8 +1113,8 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
           const bf16x8 sf = pack_acc(dp[qb], s);
 #pragma unroll
           for (int d = 0; d < DB; ++d) {
-            dv[d] = mfma(pf, lds_tr<D>(sO[cur], qb * 32 + 16 * s, d * 32, lane), dv[d]);
-            dk[d] = mfma(sf, lds_tr<D>(sQ[cur], qb * 32 + 16 * s, d * 32, lane), dk[d]);
+            dv[d] = mfma(pf, lds_col_acc<D>(sO[cur], qb * 32 + 16 * s, d * 32, lane), dv[d]);
+            dk[d] = mfma(sf, lds_col_acc<D>(sQ[cur], qb * 32 + 16 * s, d * 32, lane), dk[d]);
           }
         }
       }

@@ -59,6 +59,39 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
   return __builtin_bit_cast(unsigned short, b);
 }
 
+// two bf16 in one 32-bit word, `lo` in bits 0..15 (the lower address)
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
+  return (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16);
+}
+__device__ __forceinline__ float bf16_lo(unsigned v) { return bf16_to_f32((unsigned short)(v & 0xffffu)); }
+__device__ __forceinline__ float bf16_hi(unsigned v) { return bf16_to_f32((unsigned short)(v >> 16)); }
+
+// w[0..3] += the four bf16 of r (a residual / accumulate-into-output read)
+__device__ __forceinline__ void add_bf16x4(float (&w)[4], const u32x2& r) {
+  w[0] += bf16_lo(r[0]);
+  w[1] += bf16_hi(r[0]);
+  w[2] += bf16_lo(r[1]);
+  w[3] += bf16_hi(r[1]);
+}
+
+// Counted waits of the hand-scheduled kernels (LDS-DMA loads are invisible to hipcc: glds16 above).
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void wait_lgkmcnt0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// Workgroup id -> XCD-grouped logical id.  Hardware deals workgroup `id` to XCD id % 8; this
+// gives each XCD one contiguous range of logical ids (bijective for every n: the first n % 8
+// XCDs own one id more; cdna_hip_programming.md "XCD swizzle must be bijective").
+__device__ __forceinline__ int xcd_group_id(int id, int n) {
+  const int x = id % kNumXCD, q8 = n / kNumXCD, r8 = n % kNumXCD;
+  return (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + id / kNumXCD;
+}
+
 __device__ __forceinline__ float f16_to_f32(unsigned short h) {
   _Float16 v = __builtin_bit_cast(_Float16, h);
   return static_cast<float>(v);

@@ -180,10 +180,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmArgs p) {
   // over the 8 XCDs; the bijective remap of cdna_hip_programming.md T1 gives each XCD a
   // contiguous range of logical ids so the shared panels hit in that XCD's L2.
   int wid = blockIdx.x;
-  if (p.xcd) {
-    const int n = gridDim.x, x = wid % 8, q8 = n / 8, r8 = n % 8;
-    wid = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + wid / 8;
-  }
+  if (p.xcd) wid = xcd_group_id(wid, gridDim.x);
   const int it = wid % p.i_tiles;
   const int grp = wid / p.i_tiles;
   const int64_t i0 = (int64_t)it * BI;
@@ -276,10 +273,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmArgs p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
               const int ic = (wi * NI + a) * 32 + 8 * g + 4 * hh;  // first of the 4 i
-              const unsigned lo = (unsigned)f32_to_bf16(acc[a][b][4 * g]) |
-                                  ((unsigned)f32_to_bf16(acc[a][b][4 * g + 1]) << 16);
-              const unsigned hi = (unsigned)f32_to_bf16(acc[a][b][4 * g + 2]) |
-                                  ((unsigned)f32_to_bf16(acc[a][b][4 * g + 3]) << 16);
+              const unsigned lo = pack_bf16x2(acc[a][b][4 * g], acc[a][b][4 * g + 1]);
+              const unsigned hi = pack_bf16x2(acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
               *reinterpret_cast<u32x2*>(ot + out_off(jr, ic >> 3) + 8 * ((ic >> 2) & 1)) = u32x2{lo, hi};
             }
         }
@@ -302,10 +297,9 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmArgs p) {
               }
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                const float lo = bf16_to_f32((unsigned short)(v[e] & 0xffffu)) +
-                                 bf16_to_f32((unsigned short)(rv[e] & 0xffffu));
-                const float hi = bf16_to_f32((unsigned short)(v[e] >> 16)) + bf16_to_f32((unsigned short)(rv[e] >> 16));
-                v[e] = (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16);
+                const float lo = bf16_lo(v[e]) + bf16_lo(rv[e]);
+                const float hi = bf16_hi(v[e]) + bf16_hi(rv[e]);
+                v[e] = pack_bf16x2(lo, hi);
               }
             }
             *reinterpret_cast<u32x4*>(out + j * p.ldo + i0 + 8 * c) = v;
@@ -316,8 +310,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmArgs p) {
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {
                   const int k = 2 * e + hf;
-                  const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
-                  const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
+                  const float g = hf ? bf16_hi(v[e]) : bf16_lo(v[e]);
+                  const float yy = hf ? bf16_hi(yv[e]) : bf16_lo(yv[e]);
                   const bool on = yy * bs[k] + bh[k] > 0.f;
                   const float gm = on ? g : 0.f;
                   ssum[k] += gm;
@@ -328,8 +322,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmArgs p) {
             if constexpr (STATS) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                const float x0 = bf16_to_f32((unsigned short)(v[e] & 0xffffu));
-                const float x1 = bf16_to_f32((unsigned short)(v[e] >> 16));
+                const float x0 = bf16_lo(v[e]);
+                const float x1 = bf16_hi(v[e]);
                 ssum[2 * e] += x0;
                 ssq[2 * e] += x0 * x0;
                 ssum[2 * e + 1] += x1;
@@ -415,15 +409,10 @@ __device__ __forceinline__ void glds16_off(const void* base, unsigned voff, unsi
 
 // LDS accesses retired, then the barrier (a raw s_barrier: __syncthreads' fences would drain vmcnt)
 __device__ __forceinline__ void ring_bar() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkmcnt0();
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int N>
-__device__ __forceinline__ void vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // Wait until this wave's DMA of step u has landed.  VMEM operations retire in issue order on one counter; the
@@ -435,13 +424,13 @@ __device__ __forceinline__ void vmcnt() {
 template <int EST>
 __device__ __forceinline__ void wait_vm(bool next, int epilogues) {
   if (next) {
-    if (epilogues == 0) vmcnt<4>();
-    else if (epilogues == 1) vmcnt<4 + EST>();
-    else vmcnt<4 + 2 * EST>();
+    if (epilogues == 0) wait_vmcnt<4>();
+    else if (epilogues == 1) wait_vmcnt<4 + EST>();
+    else wait_vmcnt<4 + 2 * EST>();
   } else {
-    if (epilogues == 0) vmcnt<0>();
-    else if (epilogues == 1) vmcnt<EST>();
-    else vmcnt<2 * EST>();
+    if (epilogues == 0) wait_vmcnt<0>();
+    else if (epilogues == 1) wait_vmcnt<EST>();
+    else wait_vmcnt<2 * EST>();
   }
 }
 
@@ -468,10 +457,7 @@ __global__ __launch_bounds__(kThreads, 2) void ring_kernel(const GemmArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wi = wave / WJ, wj = wave % WJ;
   int wid = blockIdx.x;
-  if (p.xcd) {
-    const int n = gridDim.x, x = wid % 8, q8 = n / 8, r8 = n % 8;
-    wid = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + wid / 8;
-  }
+  if (p.xcd) wid = xcd_group_id(wid, gridDim.x);
   const int it = wid % p.i_tiles;
   const int grp = wid / p.i_tiles;
   const int64_t i0 = (int64_t)it * BI;
@@ -595,10 +581,8 @@ __global__ __launch_bounds__(kThreads, 2) void ring_kernel(const GemmArgs p) {
 #pragma unroll
               for (int g = 0; g < 4; ++g) {
                 const int ic = (wi * NI + a) * 32 + 8 * g + 4 * hh;  // first of the 4 i
-                const unsigned lo = (unsigned)f32_to_bf16(acc[a][b][4 * g]) |
-                                    ((unsigned)f32_to_bf16(acc[a][b][4 * g + 1]) << 16);
-                const unsigned hi = (unsigned)f32_to_bf16(acc[a][b][4 * g + 2]) |
-                                    ((unsigned)f32_to_bf16(acc[a][b][4 * g + 3]) << 16);
+                const unsigned lo = pack_bf16x2(acc[a][b][4 * g], acc[a][b][4 * g + 1]);
+                const unsigned hi = pack_bf16x2(acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
                 *reinterpret_cast<u32x2*>(ot + out_off(jr, ic >> 3) + 8 * ((ic >> 2) & 1)) = u32x2{lo, hi};
               }
           }
@@ -620,10 +604,9 @@ __global__ __launch_bounds__(kThreads, 2) void ring_kernel(const GemmArgs p) {
               }
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                const float lo = bf16_to_f32((unsigned short)(v[e] & 0xffffu)) +
-                                 bf16_to_f32((unsigned short)(rv[e] & 0xffffu));
-                const float hi = bf16_to_f32((unsigned short)(v[e] >> 16)) + bf16_to_f32((unsigned short)(rv[e] >> 16));
-                v[e] = (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16);
+                const float lo = bf16_lo(v[e]) + bf16_lo(rv[e]);
+                const float hi = bf16_hi(v[e]) + bf16_hi(rv[e]);
+                v[e] = pack_bf16x2(lo, hi);
               }
             }
             *reinterpret_cast<u32x4*>(out + j * p.ldo + i0 + 8 * c) = v;
@@ -634,8 +617,8 @@ __global__ __launch_bounds__(kThreads, 2) void ring_kernel(const GemmArgs p) {
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {
                   const int k = 2 * e + hf;
-                  const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
-                  const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
+                  const float g = hf ? bf16_hi(v[e]) : bf16_lo(v[e]);
+                  const float yy = hf ? bf16_hi(yv[e]) : bf16_lo(yv[e]);
                   const bool on = yy * bs[k] + bh[k] > 0.f;
                   const float gm = on ? g : 0.f;
                   ssum[k] += gm;
@@ -646,8 +629,8 @@ __global__ __launch_bounds__(kThreads, 2) void ring_kernel(const GemmArgs p) {
             if constexpr (STATS) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                const float x0 = bf16_to_f32((unsigned short)(v[e] & 0xffffu));
-                const float x1 = bf16_to_f32((unsigned short)(v[e] >> 16));
+                const float x0 = bf16_lo(v[e]);
+                const float x1 = bf16_hi(v[e]);
                 ssum[2 * e] += x0;
                 ssq[2 * e] += x0 * x0;
                 ssum[2 * e + 1] += x1;
@@ -757,8 +740,8 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(const float* __restri
     f32x4 acc = reinterpret_cast<const f32x4*>(slab)[v];
     for (int s = 1; s < splits; ++s) acc += reinterpret_cast<const f32x4*>(slab + (int64_t)s * n)[v];
     if constexpr (BF16) {
-      const unsigned lo = (unsigned)f32_to_bf16(acc[0]) | ((unsigned)f32_to_bf16(acc[1]) << 16);
-      const unsigned hi = (unsigned)f32_to_bf16(acc[2]) | ((unsigned)f32_to_bf16(acc[3]) << 16);
+      const unsigned lo = pack_bf16x2(acc[0], acc[1]);
+      const unsigned hi = pack_bf16x2(acc[2], acc[3]);
       reinterpret_cast<u32x2*>(dw)[v] = u32x2{lo, hi};
     } else {
       reinterpret_cast<f32x4*>(dw)[v] = acc;
@@ -909,12 +892,12 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
           const int k = 2 * e + hf;
-          const float d = bf16_to_f32((unsigned short)(hf ? sd[i][e] >> 16 : sd[i][e] & 0xffffu));
-          const float y = bf16_to_f32((unsigned short)(hf ? sy[i][e] >> 16 : sy[i][e] & 0xffffu));
+          const float d = hf ? bf16_hi(sd[i][e]) : bf16_lo(sd[i][e]);
+          const float y = hf ? bf16_hi(sy[i][e]) : bf16_lo(sy[i][e]);
           const float g = ((mb[i] >> k) & 1u) ? d : 0.f;
           v[hf] = ca[k >> 2][k & 3] * g + cb[k >> 2][k & 3] * y + cc[k >> 2][k & 3];
         }
-        o[i][e] = ((unsigned)f32_to_bf16(v[0]) | ((unsigned)f32_to_bf16(v[1]) << 16)) & keep;
+        o[i][e] = pack_bf16x2(v[0], v[1]) & keep;
       }
     }
     char* t0 = reinterpret_cast<char*>(tile_lds) + opaque((unsigned)swz<64>(r8, c8));  // as in store_a2
@@ -973,9 +956,8 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int ic = a * 32 + 8 * g + 4 * hh;  // first of the lane's 4 consecutive ci
-            const unsigned lo = (unsigned)f32_to_bf16(accd[a][4 * g]) | ((unsigned)f32_to_bf16(accd[a][4 * g + 1]) << 16);
-            const unsigned hi =
-                (unsigned)f32_to_bf16(accd[a][4 * g + 2]) | ((unsigned)f32_to_bf16(accd[a][4 * g + 3]) << 16);
+            const unsigned lo = pack_bf16x2(accd[a][4 * g], accd[a][4 * g + 1]);
+            const unsigned hi = pack_bf16x2(accd[a][4 * g + 2], accd[a][4 * g + 3]);
             *reinterpret_cast<u32x2*>(ot + out_off(jr, ic >> 3) + 8 * ((ic >> 2) & 1)) = u32x2{lo, hi};
           }
         accd[0] = accd[1] = zero16();
@@ -1006,8 +988,8 @@ __global__ __launch_bounds__(kThreads, 2) void bn3_conv3_bwd_kernel(const FusedA
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {
                   const int k = 2 * e + hf;
-                  const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
-                  const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
+                  const float g = hf ? bf16_hi(v[e]) : bf16_lo(v[e]);
+                  const float yy = hf ? bf16_hi(yv[e]) : bf16_lo(yv[e]);
                   const float gm = yy * bs[k] + bh[k] > 0.f ? g : 0.f;
                   ssum[k] += gm;
                   ssq[k] += gm * yy;

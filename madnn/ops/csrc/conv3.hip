@@ -107,11 +107,7 @@ __global__ __launch_bounds__(kThreads, CH == 32 ? 4 : 2) void conv3x3_kernel(con
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   // XCD-grouped logical id; output-channel tile fastest (co tiles of one pixel tile share its halo in L2)
-  int wid = blockIdx.x;
-  {
-    const int n = gridDim.x, x = wid % 8, q8 = n / 8, r8 = n % 8;
-    wid = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + wid / 8;
-  }
+  int wid = xcd_group_id(blockIdx.x, gridDim.x);
   const int cot = wid % p.co_tiles, mt = wid / p.co_tiles;
   const int64_t j0 = (int64_t)mt * kBJ;
   const int co0 = cot * kBI;
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(kThreads, CH == 32 ? 4 : 2) void conv3x3_kernel(con
 
   stage_halo(0);
   stage_w(0, 0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __syncthreads();
 
   const char* hbase = reinterpret_cast<const char*>(halo);
@@ -212,11 +208,11 @@ __global__ __launch_bounds__(kThreads, CH == 32 ? 4 : 2) void conv3x3_kernel(con
 #pragma unroll
         for (int b = 0; b < 2; ++b) acc[a][b] = mfma(af[a], bv[b], acc[a][b]);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();  // next weights landed; this tap's reads of the ring slot / halo are done
     if (tn == 0 && cn < nchunk) {  // next input chunk: restage the halo (every wave is past its reads)
       stage_halo(cn);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
     }
     c = cn;
@@ -234,8 +230,8 @@ __global__ __launch_bounds__(kThreads, CH == 32 ? 4 : 2) void conv3x3_kernel(con
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int ic = a * 32 + 8 * g + 4 * hh;
-        const unsigned lo = (unsigned)f32_to_bf16(acc[a][b][4 * g]) | ((unsigned)f32_to_bf16(acc[a][b][4 * g + 1]) << 16);
-        const unsigned hi = (unsigned)f32_to_bf16(acc[a][b][4 * g + 2]) | ((unsigned)f32_to_bf16(acc[a][b][4 * g + 3]) << 16);
+        const unsigned lo = pack_bf16x2(acc[a][b][4 * g], acc[a][b][4 * g + 1]);
+        const unsigned hi = pack_bf16x2(acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
         *reinterpret_cast<u32x2*>(ot + out_off(pr, ic >> 3) + 8 * ((ic >> 2) & 1)) = u32x2{lo, hi};
       }
   }
@@ -281,8 +277,8 @@ __global__ __launch_bounds__(kThreads, CH == 32 ? 4 : 2) void conv3x3_kernel(con
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
           const int k = 2 * e + hf;
-          const float g = bf16_to_f32((unsigned short)(hf ? v[e] >> 16 : v[e] & 0xffffu));
-          const float yy = bf16_to_f32((unsigned short)(hf ? yv[e] >> 16 : yv[e] & 0xffffu));
+          const float g = hf ? bf16_hi(v[e]) : bf16_lo(v[e]);
+          const float yy = hf ? bf16_hi(yv[e]) : bf16_lo(yv[e]);
           const float gm = yy * bs[k] + bh[k] > 0.f ? g : 0.f;
           ssum[k] += gm;
           ssq[k] += gm * yy;
@@ -292,8 +288,8 @@ __global__ __launch_bounds__(kThreads, CH == 32 ? 4 : 2) void conv3x3_kernel(con
     if constexpr (STATS) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float x0 = bf16_to_f32((unsigned short)(v[e] & 0xffffu));
-        const float x1 = bf16_to_f32((unsigned short)(v[e] >> 16));
+        const float x0 = bf16_lo(v[e]);
+        const float x1 = bf16_hi(v[e]);
         ssum[2 * e] += x0;
         ssq[2 * e] += x0 * x0;
         ssum[2 * e + 1] += x1;
@@ -466,8 +462,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const float* 
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < splits; ++s) acc += *reinterpret_cast<const f32x4*>(ws + (int64_t)s * n + i);
     if (bf16) {
-      const unsigned lo = (unsigned)f32_to_bf16(acc[0]) | ((unsigned)f32_to_bf16(acc[1]) << 16);
-      const unsigned hi = (unsigned)f32_to_bf16(acc[2]) | ((unsigned)f32_to_bf16(acc[3]) << 16);
+      const unsigned lo = pack_bf16x2(acc[0], acc[1]);
+      const unsigned hi = pack_bf16x2(acc[2], acc[3]);
       *reinterpret_cast<u32x2*>(static_cast<uint16_t*>(out) + i) = u32x2{lo, hi};
     } else {
       *reinterpret_cast<f32x4*>(static_cast<float*>(out) + i) = acc;

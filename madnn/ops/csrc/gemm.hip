@@ -62,22 +62,6 @@ namespace gemm {
 using namespace mf;
 using namespace k12;
 
-struct Args {
-  const uint16_t* a;
-  const uint16_t* b;
-  uint16_t* out;
-  const uint16_t* res;  // epilogue: out = y + res (same [j][i] layout, row stride ldr), or null
-  const void* bias;     // [I] fp32 (bias_f32) or bf16, or null
-  uint16_t* aux;        // pre-activation store (row stride ldx), or null
-  int64_t lda, ldb, ldo, ldr, ldx;
-  int64_t I, J, K;
-  int i_tiles, j_tiles;
-  int bias_f32, act;    // act: 0 none, 1 tanh-GELU, 2 erf-GELU
-  float* ws;            // split-K: fp32 partial slabs [splits][J][I] (null: bf16 epilogue)
-  int splits;           // workgroups per output tile along the reduction
-  int64_t kper;         // reduction elements per split (multiple of kBK)
-};
-
 template <bool A_COL, bool B_COL>
 __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
   __shared__ __attribute__((aligned(16))) uint16_t smem[kLds];
@@ -86,11 +70,9 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
   const int wr = wave >> 2, wc = wave & 3;
 
   // XCD-grouped logical id (bijective remap), i tile fastest
-  int wid = blockIdx.x;
-  {
-    const int n = gridDim.x, x = wid % 8, q8 = n / 8, r8 = n % 8;
-    wid = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + wid / 8;
-  }
+  // as k12::decode_tile, spelled out: through the helper hipcc needs 2 more SGPRs for the data- and
+  // weight-gradient instantiations
+  int wid = xcd_group_id(blockIdx.x, gridDim.x);
   const int ntile = p.i_tiles * p.j_tiles;
   const int split = wid / ntile;
   wid -= split * ntile;
@@ -152,9 +134,9 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
   for (int H = 0; H < 6; ++H)
     if (H < total) stage(H);
   if (total > 4) {
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    wait_vmcnt<4>();
   } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
   }
   barrier();
   if (wr == 1) barrier();  // group 1 runs one barrier behind
@@ -194,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) bf1[2 * c + s2] = frag16<B_COL>(sb, s2, bcol + 32 + 16 * c, lane);
       if (P + 7 < total) stage(P + 7);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the B half-tiles' last reads
+      wait_lgkmcnt0();  // the B half-tiles' last reads
       barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -212,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) af[a >> 1][2 * (a & 1) + s2] = frag16<A_COL>(sa, s2, 64 + 16 * a, lane);
       if (P + 8 < total) stage(P + 8);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the A half-tiles' last reads
+      wait_lgkmcnt0();  // the A half-tiles' last reads
       barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -227,11 +209,11 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
       // ---- Q3: no reads; retire K tile t+1's DMA (the B halves of K tile t+2 stay in flight)
       if (P + 9 < total) {
         stage(P + 9);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        wait_vmcnt<4>();
       } else if (P + 8 < total) {
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        wait_vmcnt<2>();
       } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
       }
       barrier();
       __builtin_amdgcn_s_setprio(1);
@@ -304,8 +286,8 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
         if (p.res != nullptr) rv = *reinterpret_cast<const u32x4*>(p.res + jg * p.ldr + ig);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float x0 = bf16_to_f32((unsigned short)(v[e] & 0xffffu));
-          float x1 = bf16_to_f32((unsigned short)(v[e] >> 16));
+          float x0 = bf16_lo(v[e]);
+          float x1 = bf16_hi(v[e]);
           if (p.act == kGeluErf) {
             x0 = round_bf16(gelu_erf(x0));
             x1 = round_bf16(gelu_erf(x1));
@@ -314,10 +296,10 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(const Args p) {
             x1 = round_bf16(gelu_tanh(x1));
           }
           if (p.res != nullptr) {
-            x0 += bf16_to_f32((unsigned short)(rv[e] & 0xffffu));
-            x1 += bf16_to_f32((unsigned short)(rv[e] >> 16));
+            x0 += bf16_lo(rv[e]);
+            x1 += bf16_hi(rv[e]);
           }
-          v[e] = (unsigned)f32_to_bf16(x0) | ((unsigned)f32_to_bf16(x1) << 16);
+          v[e] = pack_bf16x2(x0, x1);
         }
       }
       *reinterpret_cast<u32x4*>(p.out + jg * p.ldo + ig) = v;
@@ -341,17 +323,17 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
       const u32x4 o = *reinterpret_cast<const u32x4*>(out + e);
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
-        lo[2 * k] += bf16_to_f32((unsigned short)(o[k] & 0xffffu));
-        lo[2 * k + 1] += bf16_to_f32((unsigned short)(o[k] >> 16));
-        hi[2 * k] += bf16_to_f32((unsigned short)(o[2 + k] & 0xffffu));
-        hi[2 * k + 1] += bf16_to_f32((unsigned short)(o[2 + k] >> 16));
+        lo[2 * k] += bf16_lo(o[k]);
+        lo[2 * k + 1] += bf16_hi(o[k]);
+        hi[2 * k] += bf16_lo(o[2 + k]);
+        hi[2 * k + 1] += bf16_hi(o[2 + k]);
       }
     }
     u32x4 v;
-    v[0] = (unsigned)f32_to_bf16(lo[0]) | ((unsigned)f32_to_bf16(lo[1]) << 16);
-    v[1] = (unsigned)f32_to_bf16(lo[2]) | ((unsigned)f32_to_bf16(lo[3]) << 16);
-    v[2] = (unsigned)f32_to_bf16(hi[0]) | ((unsigned)f32_to_bf16(hi[1]) << 16);
-    v[3] = (unsigned)f32_to_bf16(hi[2]) | ((unsigned)f32_to_bf16(hi[3]) << 16);
+    v[0] = pack_bf16x2(lo[0], lo[1]);
+    v[1] = pack_bf16x2(lo[2], lo[3]);
+    v[2] = pack_bf16x2(hi[0], hi[1]);
+    v[3] = pack_bf16x2(hi[2], hi[3]);
     *reinterpret_cast<u32x4*>(out + e) = v;
   }
 }
@@ -425,23 +407,10 @@ __global__ __launch_bounds__(256, 1) void gemm4_kernel(const Args p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
 
-  int wid = blockIdx.x;
-  {
-    const int n = gridDim.x, x = wid % 8, q8 = n / 8, r8 = n % 8;
-    wid = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + wid / 8;
-  }
-  const int ntile = p.i_tiles * p.j_tiles;
-  const int split = wid / ntile;
-  wid -= split * ntile;
-  const int it = wid % p.i_tiles, jt = wid / p.i_tiles;
-  const int64_t i0 = (int64_t)it * kT, j0 = (int64_t)jt * kT;
-  const int64_t kbeg = (int64_t)split * p.kper;
-  const int64_t klen = p.K - kbeg < p.kper ? p.K - kbeg : p.kper;
-  const int nk = (int)(klen / kBK);
+  const Tile tile = decode_tile(p.i_tiles, p.j_tiles, p.K, p.kper);
+  const int split = tile.split, nk = tile.nk;
+  const int64_t i0 = tile.i0, j0 = tile.j0, kbeg = tile.kbeg;
 
-  // this wave's DMA half-tile (0, 1: A halves; 2, 3: B halves): 8 per-lane byte offsets (rows
-  // 4e .. 4e + 3 of a 32-row part, relative to the part's first row, column 0: the clamped columns of a
-  // ragged edge tile lie left of x0, and the saddr offset is unsigned) and the uniform part bases
   const bool isA = wave < 2;
   const uint16_t* const op = isA ? p.a : p.b;
   const int64_t ld = isA ? p.lda : p.ldb;
@@ -452,8 +421,6 @@ __global__ __launch_bounds__(256, 1) void gemm4_kernel(const Args p) {
   const char* const gbase = reinterpret_cast<const char*>(op + kbeg * ld);
   const int64_t tbytes = (int64_t)kBK * ld * 2, pbytes = (int64_t)32 * ld * 2;
   const unsigned ldsw = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(smem + 2 * wave * kHalf));
-  // piece e of part `part` of the K tile at tb (= gbase + t * tbytes) into stage ST: LDS bytes
-  // (2w + ST) * 16 KiB + part * 8 KiB + e * 1 KiB
   auto dma1 = [&](const char* tb, auto st_c, auto part_c, auto e_c) {
     constexpr unsigned o = decltype(st_c)::value * kHalf * 2 + decltype(part_c)::value * 8192 + decltype(e_c)::value * 1024;
     glds16_one<o>(tb + decltype(part_c)::value * pbytes, ldsw, voff[decltype(e_c)::value]);
@@ -502,13 +469,8 @@ __global__ __launch_bounds__(256, 1) void gemm4_kernel(const Args p) {
       }
     }
   }
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
   auto frag = [&](const unsigned (&ad)[2], auto st_c, auto ks_c) {
-    constexpr int imm = decltype(st_c)::value * kHalf * 2 + decltype(ks_c)::value * 4096;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(size_t)(ad[0] + imm));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(size_t)(ad[1] + imm));
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
+    return frag_tr<decltype(st_c)::value * kHalf * 2 + decltype(ks_c)::value * 4096>(ad);
   };
   // fragment f of the next phase, in the order its first MFMAs consume them: A0, B0..B3, A1..A3
   auto rdf = [&](bf16x8 (&fa)[4], bf16x8 (&fb)[4], auto st_c, auto ks_c, int f) {
@@ -534,7 +496,7 @@ __global__ __launch_bounds__(256, 1) void gemm4_kernel(const Args p) {
   dma_half(tbp, C1{}, C0{}, C0{});
   dma_half(tbp, C1{}, C0{}, C4{});
   dma_half(tbp, C1{}, C1{}, C0{});
-  asm volatile("s_waitcnt vmcnt(20)" ::: "memory");   // K0(0)
+  wait_vmcnt<20>();   // K0(0)
   barrier();
 #pragma unroll
   for (int f = 0; f < 8; ++f) rdf(fa0, fb0, C0{}, C0{}, f);
@@ -562,8 +524,8 @@ __global__ __launch_bounds__(256, 1) void gemm4_kernel(const Args p) {
     for (int q = 0; q < 16; ++q) {
       ac[q >> 2][q & 3] = mf::mfma(fc[q >> 2], gc[q & 3], ac[q >> 2][q & 3]);
       if (q == 2) {
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_vmcnt<16>();
+        wait_lgkmcnt0();
         barrier();
       } else if (q == 3) dma1(tb, st_c, part_c, C0{});
       else if (q == 5) dma1(tb, st_c, part_c, C1{});
@@ -596,7 +558,7 @@ __global__ __launch_bounds__(256, 1) void gemm4_kernel(const Args p) {
     ktile(t + 1, C1{});
   }
   if (t < nk) ktile(t, C0{});
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped reloads
+  wait_vmcnt<0>();   // the clamped reloads
   }
 
   const int h = lane >> 5, l32 = lane & 31;
@@ -629,8 +591,8 @@ __global__ __launch_bounds__(256, 1) void gemm4_kernel(const Args p) {
         w[2] += bf16_to_f32((unsigned short)(r[1] & 0xffffu));
         w[3] += bf16_to_f32((unsigned short)(r[1] >> 16));
       }
-      const unsigned lo = (unsigned)f32_to_bf16(w[0]) | ((unsigned)f32_to_bf16(w[1]) << 16);
-      const unsigned hi = (unsigned)f32_to_bf16(w[2]) | ((unsigned)f32_to_bf16(w[3]) << 16);
+      const unsigned lo = pack_bf16x2(w[0], w[1]);
+      const unsigned hi = pack_bf16x2(w[2], w[3]);
       *reinterpret_cast<u32x2*>(p.out + jg * p.ldo + ig) = u32x2{lo, hi};
     }
   });
@@ -674,19 +636,9 @@ __global__ __launch_bounds__(256, 1) void gemm4h_kernel(const Args p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
 
-  int wid = blockIdx.x;
-  {
-    const int n = gridDim.x, x = wid % 8, q8 = n / 8, r8 = n % 8;
-    wid = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + wid / 8;
-  }
-  const int ntile = p.i_tiles * p.j_tiles;
-  const int split = wid / ntile;
-  wid -= split * ntile;
-  const int it = wid % p.i_tiles, jt = wid / p.i_tiles;
-  const int64_t i0 = (int64_t)it * kT, j0 = (int64_t)jt * kT;
-  const int64_t kbeg = (int64_t)split * p.kper;
-  const int64_t klen = p.K - kbeg < p.kper ? p.K - kbeg : p.kper;
-  const int nk = (int)(klen / kBK);
+  const Tile tile = decode_tile(p.i_tiles, p.j_tiles, p.K, p.kper);
+  const int split = tile.split, nk = tile.nk;
+  const int64_t i0 = tile.i0, j0 = tile.j0, kbeg = tile.kbeg;
 
   const bool isA = wave < 2;
   const uint16_t* const op = isA ? p.a : p.b;
@@ -741,13 +693,8 @@ __global__ __launch_bounds__(256, 1) void gemm4h_kernel(const Args p) {
       }
     }
   }
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
   auto frag = [&](const unsigned (&ad)[2], auto st_c, auto s_c) {
-    constexpr int imm = decltype(st_c)::value * kHalf * 2 + decltype(s_c)::value * 8192;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(size_t)(ad[0] + imm));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(size_t)(ad[1] + imm));
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
+    return frag_tr<decltype(st_c)::value * kHalf * 2 + decltype(s_c)::value * 8192>(ad);
   };
   bf16x8 fa0[8], fb0[8], fa1[8], fb1[8];
 
@@ -757,7 +704,7 @@ __global__ __launch_bounds__(256, 1) void gemm4h_kernel(const Args p) {
   dma_part(gbase, C0{}, C1{});
   dma_part(tb1, C1{}, C0{});
   dma_part(tb1, C1{}, C1{});
-  asm volatile("s_waitcnt vmcnt(24)" ::: "memory");   // K0(0)
+  wait_vmcnt<24>();   // K0(0)
   barrier();
 #pragma unroll
   for (int x = 0; x < 8; ++x) {
@@ -775,8 +722,8 @@ __global__ __launch_bounds__(256, 1) void gemm4h_kernel(const Args p) {
       constexpr int q = decltype(q_c)::value;
       mfma16a(ac[q >> 3][q & 7], fc[q >> 3], gc[q & 7]);
       if constexpr (q == 2) {
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_vmcnt<16>();
+        wait_lgkmcnt0();
         barrier();
       }
       if constexpr (q >= 3 && q <= 31 && (q - 3) % 4 == 0)
@@ -805,7 +752,7 @@ __global__ __launch_bounds__(256, 1) void gemm4h_kernel(const Args p) {
     ktile(t, C0{});
     ktile(t + 1, C1{});
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped reloads
+  wait_vmcnt<0>();   // the clamped reloads
   mfma_drain();   // inside the branch: the join block after it may already copy accumulators
   }
 
@@ -837,22 +784,56 @@ __global__ __launch_bounds__(256, 1) void gemm4h_kernel(const Args p) {
           w[2] += bf16_to_f32((unsigned short)(r[1] & 0xffffu));
           w[3] += bf16_to_f32((unsigned short)(r[1] >> 16));
         }
-        const unsigned lo = (unsigned)f32_to_bf16(w[0]) | ((unsigned)f32_to_bf16(w[1]) << 16);
-        const unsigned hi = (unsigned)f32_to_bf16(w[2]) | ((unsigned)f32_to_bf16(w[3]) << 16);
+        const unsigned lo = pack_bf16x2(w[0], w[1]);
+        const unsigned hi = pack_bf16x2(w[2], w[3]);
         *reinterpret_cast<u32x2*>(p.out + jg * p.ldo + ig) = u32x2{lo, hi};
       }
     }
 }
 
-template <bool A_COL, bool B_COL>
-hipError_t launch(Args& p, hipStream_t s) {
+// The one place that lays a problem out on the grid: i_tiles / j_tiles, then `splits` workgroups per tile.
+template <class Kernel>
+hipError_t launch(Kernel kernel, int threads, Args& p, hipStream_t s) {
   p.i_tiles = (int)((p.I + kT - 1) / kT);
   p.j_tiles = (int)((p.J + kT - 1) / kT);
   if (p.splits < 1) p.splits = 1;
   if (p.kper <= 0) p.kper = p.K;
   const int64_t grid = (int64_t)p.i_tiles * p.j_tiles * p.splits;
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((gemm_kernel<A_COL, B_COL>), dim3((unsigned)grid), dim3(kThreads), 0, s, p);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), 0, s, p);
+  return hipGetLastError();
+}
+
+// dW[n][k] (+)= sum_m dY[m][n] X[m][k] as a K12 problem: i = k, j = n, reduction over the m tokens, both
+// operands column memory.  Every split gets a multiple of `unit` K tiles (K12W16: 2).
+static Args wgrad_args(const void* dy, const void* x, void* dw, float* ws, int splits, int accumulate, int64_t M,
+                       int64_t N, int64_t K, int unit) {
+  Args p{};
+  p.a = static_cast<const uint16_t*>(x);   // A[i = k][kk = m] = X[m][k]
+  p.lda = K;
+  p.b = static_cast<const uint16_t*>(dy);  // B[kk = m][j = n] = dY[m][n]
+  p.ldb = N;
+  p.out = static_cast<uint16_t*>(dw);
+  p.ldo = K;
+  p.res = accumulate && splits <= 1 ? static_cast<const uint16_t*>(dw) : nullptr;
+  p.ldr = K;
+  p.I = K;
+  p.J = N;
+  p.K = M;
+  p.splits = splits > 1 ? splits : 1;
+  const int64_t units = M / (unit * kBK);
+  p.kper = ((units + p.splits - 1) / p.splits) * unit * kBK;
+  p.ws = p.splits > 1 ? ws : nullptr;
+  return p;
+}
+
+// the second pass of a split weight gradient: slabs -> bf16 dW (+ the existing dW)
+static hipError_t reduce_splits(const Args& p, int accumulate, hipStream_t s) {
+  const int64_t n = p.I * p.J;
+  int64_t blocks = (n / 8 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p.ws, p.out, p.splits, n,
+                     accumulate);
   return hipGetLastError();
 }
 
@@ -892,7 +873,7 @@ hipError_t madnn_linear_fwd(const void* x, const void* w, const void* bias, int 
   p.I = N;
   p.J = M;
   p.K = K;
-  return launch<false, false>(p, s);
+  return launch(gemm_kernel<false, false>, kThreads, p, s);
 }
 
 // dX[m][k] = dY[m][n] W[n][k] (+ res[m][k]; res may alias dX for in-place accumulation)
@@ -911,7 +892,7 @@ hipError_t madnn_linear_dgrad(const void* dy, const void* w, const void* res, vo
   p.I = K;
   p.J = M;
   p.K = N;
-  return launch<true, false>(p, s);
+  return launch(gemm_kernel<true, false>, kThreads, p, s);
 }
 
 // Workgroups per output tile for a weight gradient: 256 CUs, one 128-KiB-LDS workgroup per CU.
@@ -941,30 +922,9 @@ hipError_t madnn_linear_wgrad(const void* dy, const void* x, void* dw, float* ws
                               int64_t M, int64_t N, int64_t K, hipStream_t s) {
   if (M % kBK || !madnn_gemm_supported(K, N, M, K, N)) return hipErrorInvalidValue;
   if (splits > 1 && ws == nullptr) return hipErrorInvalidValue;
-  Args p{};
-  p.a = static_cast<const uint16_t*>(x);   // A[i = k][kk = m] = X[m][k]: column memory
-  p.lda = K;
-  p.b = static_cast<const uint16_t*>(dy);  // B[kk = m][j = n] = dY[m][n]: column memory
-  p.ldb = N;
-  p.out = static_cast<uint16_t*>(dw);
-  p.ldo = K;
-  p.res = accumulate && splits <= 1 ? static_cast<const uint16_t*>(dw) : nullptr;
-  p.ldr = K;
-  p.I = K;
-  p.J = N;
-  p.K = M;
-  p.splits = splits > 1 ? splits : 1;
-  const int64_t nk = M / kBK;
-  p.kper = ((nk + p.splits - 1) / p.splits) * kBK;
-  p.ws = p.splits > 1 ? ws : nullptr;
-  hipError_t e = launch<true, true>(p, s);
-  if (e != hipSuccess || p.splits == 1) return e;
-  const int64_t n = N * K;
-  int64_t blocks = (n / 8 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ws, static_cast<uint16_t*>(dw),
-                     p.splits, n, accumulate);
-  return hipGetLastError();
+  Args p = wgrad_args(dy, x, dw, ws, splits, accumulate, M, N, K, 1);
+  const hipError_t e = launch(gemm_kernel<true, true>, kThreads, p, s);
+  return e != hipSuccess || p.splits == 1 ? e : reduce_splits(p, accumulate, s);
 }
 
 // K12W weight gradient (same contract as madnn_linear_wgrad; the split count from madnn_wgrad_splits).
@@ -975,45 +935,12 @@ static hipError_t linear_wgrad4_launch(const void* dy, const void* x, void* dw, 
   if (M % kBK || !madnn_gemm_supported(K, N, M, K, N)) return hipErrorInvalidValue;
   if (mfma16 && M % (2 * kBK)) return hipErrorInvalidValue;
   if (splits > 1 && ws == nullptr) return hipErrorInvalidValue;
-  Args p{};
-  p.a = static_cast<const uint16_t*>(x);
-  p.lda = K;
-  p.b = static_cast<const uint16_t*>(dy);
-  p.ldb = N;
-  p.out = static_cast<uint16_t*>(dw);
-  p.ldo = K;
-  p.res = accumulate && splits <= 1 ? static_cast<const uint16_t*>(dw) : nullptr;
-  p.ldr = K;
-  p.I = K;
-  p.J = N;
-  p.K = M;
-  p.splits = splits > 1 ? splits : 1;
-  if (mfma16) {
-    const int64_t pairs = M / (2 * kBK);
-    p.kper = ((pairs + p.splits - 1) / p.splits) * 2 * kBK;
-  } else {
-    const int64_t nk = M / kBK;
-    p.kper = ((nk + p.splits - 1) / p.splits) * kBK;
-  }
-  p.ws = p.splits > 1 ? ws : nullptr;
-  p.i_tiles = (int)((p.I + kT - 1) / kT);
-  p.j_tiles = (int)((p.J + kT - 1) / kT);
-  const int64_t grid = (int64_t)p.i_tiles * p.j_tiles * p.splits;
-  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  Args p = wgrad_args(dy, x, dw, ws, splits, accumulate, M, N, K, mfma16 ? 2 : 1);
   // saddr DMA: per-lane 32-bit byte offsets (31 rows + a column) within a 32-row part
   if ((p.lda > p.ldb ? p.lda : p.ldb) >= ((int64_t)1 << 25) || p.I > p.lda || p.J > p.ldb) return hipErrorInvalidValue;
-  if (mfma16)
-    hipLaunchKernelGGL((gemm4h_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((gemm4_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, s, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || p.splits == 1) return e;
-  const int64_t n = N * K;
-  int64_t blocks = (n / 8 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ws, static_cast<uint16_t*>(dw),
-                     p.splits, n, accumulate);
-  return hipGetLastError();
+  const hipError_t e =
+      mfma16 ? launch(gemm4h_kernel<true, true>, 256, p, s) : launch(gemm4_kernel<true, true>, 256, p, s);
+  return e != hipSuccess || p.splits == 1 ? e : reduce_splits(p, accumulate, s);
 }
 
 hipError_t madnn_linear_wgrad4(const void* dy, const void* x, void* dw, float* ws, int splits, int accumulate,

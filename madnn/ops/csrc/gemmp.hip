@@ -67,12 +67,6 @@ struct PArgs {
   int bias_f32;
 };
 
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
-}
-__device__ __forceinline__ float lo16(unsigned v) { return bf16_to_f32((unsigned short)(v & 0xffffu)); }
-__device__ __forceinline__ float hi16(unsigned v) { return bf16_to_f32((unsigned short)(v >> 16)); }
-
 // two accumulator blocks X, Y (4 rows each per lane: rows 4g..4g+3 of a 16-row block, g = lane >> 4)
 // as packed bf16 pairs -> this lane's 8 consecutive rows: X rows 8(g>>1).. for even g, Y's for odd g
 __device__ __forceinline__ u32x4 swap_pairs(unsigned x0, unsigned x1, unsigned y0, unsigned y1) {
@@ -206,9 +200,9 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
     stage_next(P3{});
   }
   if (total > 4) {
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    wait_vmcnt<4>();
   } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
   }
   barrier();
   if (wr == 1) barrier();  // group 1 runs one barrier behind, across every tile
@@ -251,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) bf1[2 * c + s2] = frag16<B_COL>(sb, s2, bcol + 32 + 16 * c, lane);
       if (!first && cur_H < total) stage_next(P1{});
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the B half-tiles' last reads
+      wait_lgkmcnt0();  // the B half-tiles' last reads
       barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -269,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) af[a >> 1][2 * (a & 1) + s2] = frag16<A_COL>(sa, s2, 64 + 16 * a, lane);
       if (cur_H < total) stage_next(P2{});
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the A half-tiles' last reads
+      wait_lgkmcnt0();  // the A half-tiles' last reads
       barrier();
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -286,19 +280,19 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
       if (first) {
         if (P + 9 < total) {
           stage_next(P3{});
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S + 4) : "memory");
+          wait_vmcnt<S + 4>();
         } else if (P + 8 < total) {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S + 2) : "memory");
+          wait_vmcnt<S + 2>();
         } else {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S) : "memory");
+          wait_vmcnt<S>();
         }
       } else if (P + 9 < total) {
         stage_next(P3{});
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        wait_vmcnt<4>();
       } else if (P + 8 < total) {
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        wait_vmcnt<2>();
       } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
       }
       barrier();
       __builtin_amdgcn_s_setprio(1);
@@ -353,14 +347,15 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
             const f32x4 X = ac4[2 * m][b], Y = ac4[2 * m + 1][b];
-            const u32x4 d = swap_pairs(pack2(X[0], X[1]), pack2(X[2], X[3]), pack2(Y[0], Y[1]), pack2(Y[2], Y[3]));
+            const u32x4 d = swap_pairs(pack_bf16x2(X[0], X[1]), pack_bf16x2(X[2], X[3]), pack_bf16x2(Y[0], Y[1]),
+                                       pack_bf16x2(Y[2], Y[3]));
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              const float v0 = lo16(d[k]) * gelu_act_grad<GK>(lo16(pv[mm][b][k]));
-              const float v1 = hi16(d[k]) * gelu_act_grad<GK>(hi16(pv[mm][b][k]));
+              const float v0 = bf16_lo(d[k]) * gelu_act_grad<GK>(bf16_lo(pv[mm][b][k]));
+              const float v1 = bf16_hi(d[k]) * gelu_act_grad<GK>(bf16_hi(pv[mm][b][k]));
               cs[2 * k] += v0;
               cs[2 * k + 1] += v1;
-              ov[mm][b][k] = pack2(v0, v1);
+              ov[mm][b][k] = pack_bf16x2(v0, v1);
             }
           }
           cv[mm] = colsum64(cs, el16);  // over this wave's 64 rows
@@ -398,11 +393,12 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           const f32x4 X = ac4[2 * m][b], Y = ac4[2 * m + 1][b];
-          const u32x4 h = swap_pairs(pack2(X[0], X[1]), pack2(X[2], X[3]), pack2(Y[0], Y[1]), pack2(Y[2], Y[3]));
+          const u32x4 h = swap_pairs(pack_bf16x2(X[0], X[1]), pack_bf16x2(X[2], X[3]), pack_bf16x2(Y[0], Y[1]),
+                                     pack_bf16x2(Y[2], Y[3]));
           *reinterpret_cast<u32x4*>(p.out + (jb + 16 * b) * p.ldo + ib + 32 * m + io) = h;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const float v0 = lo16(h[k]), v1 = hi16(h[k]);  // the stored (bf16-rounded) values
+            const float v0 = bf16_lo(h[k]), v1 = bf16_hi(h[k]);  // the stored (bf16-rounded) values
             cs[2 * k] += v0;
             cs[2 * k + 1] += v1;
             cq[2 * k] += v0 * v0;
@@ -430,14 +426,14 @@ __global__ __launch_bounds__(kThreads) void gemmp_kernel(const PArgs p) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           const f32x4 X = ac4[2 * m][b], Y = ac4[2 * m + 1][b];
-          const u32x4 h = swap_pairs(pack2(X[0] + bx[0], X[1] + bx[1]), pack2(X[2] + bx[2], X[3] + bx[3]),
-                                     pack2(Y[0] + by[0], Y[1] + by[1]), pack2(Y[2] + by[2], Y[3] + by[3]));
+          const u32x4 h = swap_pairs(pack_bf16x2(X[0] + bx[0], X[1] + bx[1]), pack_bf16x2(X[2] + bx[2], X[3] + bx[3]),
+                                     pack_bf16x2(Y[0] + by[0], Y[1] + by[1]), pack_bf16x2(Y[2] + by[2], Y[3] + by[3]));
           uint16_t* dst = p.out + (jb + 16 * b) * p.ldo + ib + 32 * m + io;
           if constexpr (EPI == kGelu) {
             *reinterpret_cast<u32x4*>(p.aux + (jb + 16 * b) * p.ldo + ib + 32 * m + io) = h;
             u32x4 o;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = pack2(gelu_act<GK>(lo16(h[k])), gelu_act<GK>(hi16(h[k])));
+            for (int k = 0; k < 4; ++k) o[k] = pack_bf16x2(gelu_act<GK>(bf16_lo(h[k])), gelu_act<GK>(bf16_hi(h[k])));
             *reinterpret_cast<u32x4*>(dst) = o;
           } else {
             *reinterpret_cast<u32x4*>(dst) = h;

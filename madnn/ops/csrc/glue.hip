@@ -27,21 +27,18 @@
 namespace madnn {
 namespace glue {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void unpack8(const u32x4& v, float (&f)[8]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    f[2 * j] = bf16_to_f32((unsigned short)(v[j] & 0xffffu));
-    f[2 * j + 1] = bf16_to_f32((unsigned short)(v[j] >> 16));
+    f[2 * j] = bf16_lo(v[j]);
+    f[2 * j + 1] = bf16_hi(v[j]);
   }
 }
 
 __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
   u32x4 v;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = (unsigned)f32_to_bf16(f[2 * j]) | ((unsigned)f32_to_bf16(f[2 * j + 1]) << 16);
+  for (int j = 0; j < 4; ++j) v[j] = pack_bf16x2(f[2 * j], f[2 * j + 1]);
   return v;
 }
 

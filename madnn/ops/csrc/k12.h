@@ -1,7 +1,8 @@
 // K12 building blocks shared by the 256x256 LDS-DMA GEMM kernels (gemm.hip: one tile per
-// workgroup; gemmp.hip: persistent, epilogues overlapped with the next tile's loads): tile
-// constants, the per-lane DMA source offsets of the XOR-swizzled LDS images and the
-// v_mfma_f32_16x16x32_bf16 fragment reads.  Layout derivation: gemm.hip header.
+// workgroup, K12 / K12W / K12W16; gemmp.hip: persistent, epilogues overlapped with the next tile's
+// loads): tile constants, the kernel arguments and the workgroup -> tile decode, the per-lane DMA
+// source offsets of the XOR-swizzled LDS images and the fragment reads.  Layout and schedule
+// derivation: gemm.hip header.
 #pragma once
 
 #include "gelu.h"
@@ -19,6 +20,41 @@ constexpr int kHalf = 128 * kBK;         // bf16 elements of one half-tile (16 K
 constexpr int kStage = 4 * kHalf;        // A0 A1 B0 B1
 constexpr int kLds = 2 * kStage;         // 128 KiB
 
+struct Args {
+  const uint16_t* a;
+  const uint16_t* b;
+  uint16_t* out;
+  const uint16_t* res;  // epilogue: out = y + res (same [j][i] layout, row stride ldr), or null
+  const void* bias;     // [I] fp32 (bias_f32) or bf16, or null
+  uint16_t* aux;        // pre-activation store (row stride ldx), or null
+  int64_t lda, ldb, ldo, ldr, ldx;
+  int64_t I, J, K;
+  int i_tiles, j_tiles;
+  int bias_f32, act;    // act: 0 none, 1 tanh-GELU, 2 erf-GELU
+  float* ws;            // split-K: fp32 partial slabs [splits][J][I] (null: bf16 epilogue)
+  int splits;           // workgroups per output tile along the reduction
+  int64_t kper;         // reduction elements per split (multiple of kBK)
+};
+
+// This workgroup's share of an Args problem: XCD-grouped logical id (common.h), i tile fastest, then
+// the split; `nk` K tiles from reduction element kbeg.  Returned by value and copied to scalars by the
+// kernels: what a lambda captures must not be the argument struct (hipcc spills it to scratch).
+// K12W and K12W16 use it; K12's own gemm_kernel keeps the same lines spelled out (gemm.hip says why).
+struct Tile {
+  int split;
+  int64_t i0, j0, kbeg;
+  int nk;
+};
+__device__ __forceinline__ Tile decode_tile(int i_tiles, int j_tiles, int64_t K, int64_t kper) {
+  int wid = xcd_group_id(blockIdx.x, gridDim.x);
+  const int ntile = i_tiles * j_tiles;
+  const int split = wid / ntile;
+  wid -= split * ntile;
+  const int it = wid % i_tiles, jt = wid / i_tiles;
+  const int64_t kbeg = (int64_t)split * kper;
+  const int64_t klen = K - kbeg < kper ? K - kbeg : kper;
+  return Tile{split, (int64_t)it * kT, (int64_t)jt * kT, kbeg, (int)(klen / kBK)};
+}
 
 __device__ __forceinline__ void barrier() {
   __builtin_amdgcn_sched_barrier(0);
@@ -75,11 +111,9 @@ __device__ __forceinline__ bf16x8 frag16(const uint16_t* tile, int s, int x, int
     const int row = 32 * s + 8 * g + (i >> 2);
     const char* base = reinterpret_cast<const char*>(tile);
     const int sub = 8 * ((col >> 2) & 1);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + swz<128>(row, col >> 3) + sub));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + swz<128>(row + 4, col >> 3) + sub));
-    const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
+    return join_tr(lo, hi);
   } else {
     const int row = x + (lane & 15);
     return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(tile) + swz16(row, 4 * s + (lane >> 4)));
@@ -87,6 +121,14 @@ __device__ __forceinline__ bf16x8 frag16(const uint16_t* tile, int s, int x, int
 }
 
 __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+// transposed-pair fragment read from two per-lane LDS byte addresses (row quads lo / hi) + an immediate
+template <int IMM>
+__device__ __forceinline__ bf16x8 frag_tr(const unsigned (&ad)[2]) {
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(size_t)(ad[0] + IMM));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(size_t)(ad[1] + IMM));
+  return join_tr(lo, hi);
+}
 
 }  // namespace k12
 }  // namespace madnn

@@ -109,6 +109,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const void* __restrict
 // the k3s2 kernels renumber workgroups to give each XCD one contiguous 1/8 of every
 // grid-stride sweep: neighbours then hit the same L2 instead of fetching the shared row
 // from HBM twice (MI355X_MICROARCH.md "XCD").  Needs gridDim.x % 8 == 0 (host guarantees).
+// Not common.h's xcd_group_id: that one is bijective for any grid; this is its n % 8 == 0 case, switchable per launch.
 __device__ __forceinline__ unsigned xcd_block_id(int swz) {
   if (!swz) return blockIdx.x;
   return (blockIdx.x % kNumXCD) * (gridDim.x / kNumXCD) + blockIdx.x / kNumXCD;

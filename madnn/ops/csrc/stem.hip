@@ -144,8 +144,8 @@ __global__ __launch_bounds__(kThreads, 2) void stem_fwd_kernel(const StemArgs a)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int co = 32 * nb + 8 * g + 4 * hh;
-        const unsigned lo = (unsigned)f32_to_bf16(acc[q][4 * g]) | ((unsigned)f32_to_bf16(acc[q][4 * g + 1]) << 16);
-        const unsigned hi = (unsigned)f32_to_bf16(acc[q][4 * g + 2]) | ((unsigned)f32_to_bf16(acc[q][4 * g + 3]) << 16);
+        const unsigned lo = pack_bf16x2(acc[q][4 * g], acc[q][4 * g + 1]);
+        const unsigned hi = pack_bf16x2(acc[q][4 * g + 2], acc[q][4 * g + 3]);
         *reinterpret_cast<u32x2*>(otile + pix * 128 + 16 * ((co >> 3) ^ ((pix >> 1) & 7)) + 8 * ((co >> 2) & 1)) =
             u32x2{lo, hi};
       }
@@ -160,8 +160,8 @@ __global__ __launch_bounds__(kThreads, 2) void stem_fwd_kernel(const StemArgs a)
         if constexpr (STATS) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float x0 = bf16_to_f32((unsigned short)(v[e] & 0xffffu));
-            const float x1 = bf16_to_f32((unsigned short)(v[e] >> 16));
+            const float x0 = bf16_lo(v[e]);
+            const float x1 = bf16_hi(v[e]);
             ssum[2 * e] += x0;
             ssq[2 * e] += x0 * x0;
             ssum[2 * e + 1] += x1;
@@ -415,11 +415,11 @@ __global__ __launch_bounds__(kThreads, 2) void stem_wgrad_kernel(const StemWArgs
             float acc = 0.f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const float gj = bf16_to_f32((unsigned short)((g[q][j >> 1] >> (16 * (j & 1))) & 0xffffu));
+              const float gj = bf16_lo(g[q][j >> 1] >> (16 * (j & 1)));
               const unsigned byte = (pk[q][j >> 2] >> (8 * (j & 3))) & 0xffu;
               if (ok[q]) acc += (byte == pos[q]) ? gj : 0.f;
             }
-            const float yv = bf16_to_f32((unsigned short)((dstg[i][j >> 1] >> (16 * (j & 1))) & 0xffffu));
+            const float yv = bf16_lo(dstg[i][j >> 1] >> (16 * (j & 1)));
             const float z = yv * v[0][j] + v[1][j];
             acc = z > 0.f ? acc : 0.f;
             ob[e] = f32_to_bf16(v[2][j] * acc + v[3][j] * yv + v[4][j]);
