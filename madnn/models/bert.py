@@ -86,18 +86,21 @@ class BertLayer(nn.Module):
     def tensor_parallel_pairs(self):
         return [(("fc1",), "fc2")]
 
-    def forward(self, x):
+    def forward(self, x, seqlens=None):
+        """``seqlens`` (int32 [B], optional): the valid lengths of a right-padded batch, handed to the
+        attention (:meth:`SelfAttention.forward`); every other op of the layer works per position."""
         p = self.drop.p if self.training else 0.0
         if p > 0.0 and ops.hidden_dropout_supported(x, x.size(-1), p):
-            return self._forward_drop(x, p)
+            return self._forward_drop(x, p, seqlens)
         fused = p == 0.0 and ops.FUSED_LINEAR
         if fused and type(self.attn) is SelfAttention:
             # LN(x + attn(x)): x's residual gradient is summed inside the QKV projection's data-gradient
             # GEMM (ops.linear_tee), not by a separate pass over x's two gradients
-            a, xr = self.attn.forward_tee(x)
+            a, xr = self.attn.forward_tee(x, seqlens)
             y, _ = self.attn_norm(a, residual=xr)
         else:
-            y, _ = self.attn_norm(self.drop(self.attn(x)), residual=x)
+            a = self.attn(x, seqlens) if seqlens is not None else self.attn(x)
+            y, _ = self.attn_norm(self.drop(a), residual=x)
         if fused and type(self.fc1) is nn.Linear and type(self.fc2) is nn.Linear:
             # one fused autograd node: the exact GELU and its backward in the two GEMMs' epilogues, the
             # residual y added in fc2's epilogue and its gradient inside y's data-gradient GEMM
@@ -108,15 +111,15 @@ class BertLayer(nn.Module):
         z, _ = self.ffn_norm(h, residual=y)
         return z
 
-    def _forward_drop(self, x, p):
+    def _forward_drop(self, x, p, seqlens=None):
         """Training with hidden dropout: both dropouts run inside the two LayerNorm kernels (K3 with
         ``dropout_p``), so the fused paths of the dropout-free layer stay: ``forward_tee`` and the
         one-node MLP.  The MLP's residual y is added by ffn_norm (after the dropout), so y gets two
         gradients that autograd sums."""
         if ops.FUSED_LINEAR and type(self.attn) is SelfAttention:
-            a, xr = self.attn.forward_tee(x)
+            a, xr = self.attn.forward_tee(x, seqlens)
         else:
-            a, xr = self.attn(x), x
+            a, xr = (self.attn(x, seqlens) if seqlens is not None else self.attn(x)), x
         y, _ = self.attn_norm(a, residual=xr, dropout_p=p)
         if ops.FUSED_LINEAR and type(self.fc1) is nn.Linear and type(self.fc2) is nn.Linear:
             h = ops.gelu_mlp(y, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, residual=None,
@@ -148,10 +151,15 @@ class BertForPreTraining(nn.Module):
         self.head = BertMLMHead(cfg, self.embed.word)
         init_normal_(self)
 
-    def forward(self, ids):
+    def forward(self, ids, seqlens=None):
+        """Logits [B, S, padded_vocab].  ``seqlens`` (int32 [B] on ids' device, optional): ``ids`` is a
+        right-padded batch, sequence ``b`` has ``seqlens[b]`` real tokens.  The logits at the valid
+        positions are then those of each sequence run alone at its true length; the logits at padded
+        positions are meaningless and the loss has to ignore them.  Lengths are not carried through
+        :meth:`pipeline_layers` / the pipeline engines (stages exchange one tensor): out of scope."""
         x = self.embed(ids)
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x) if seqlens is None else layer(x, seqlens)
         return self.head(x)
 
     @staticmethod

@@ -62,20 +62,23 @@ class SelfAttention(nn.Module):
         self.qkv = nn.Linear(hidden, (heads + 2 * self.kv_heads) * self.head_dim, bias=bias)
         self.proj = nn.Linear(heads * self.head_dim, hidden, bias=bias)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, seqlens=None) -> torch.Tensor:
+        """``seqlens`` (int32 [B] on x's device, optional): a right-padded batch, the contract of
+        :func:`ops.attention` -- valid rows attend to their sequence's valid keys only, the attention
+        output of padded rows is zero (the output projection then leaves its bias there)."""
         b, s, _ = x.shape
-        return self.attend(linear(self.qkv, x), b, s)
+        return self.attend(linear(self.qkv, x), b, s, seqlens)
 
-    def forward_tee(self, x: torch.Tensor):
+    def forward_tee(self, x: torch.Tensor, seqlens=None):
         """``(attn(x), x')``: the QKV projection through :func:`ops.linear_tee`, so a residual path
         that uses ``x'`` has its gradient summed inside the projection's data-gradient GEMM."""
         b, s, _ = x.shape
         if ops.FUSED_LINEAR and type(self.qkv) is nn.Linear:
             qkv, xr = ops.linear_tee(x, self.qkv.weight, self.qkv.bias)
-            return self.attend(qkv, b, s), xr
-        return self.forward(x), x
+            return self.attend(qkv, b, s, seqlens), xr
+        return self.forward(x, seqlens), x
 
-    def attend(self, qkv: torch.Tensor, b: int, s: int) -> torch.Tensor:
+    def attend(self, qkv: torch.Tensor, b: int, s: int, seqlens=None) -> torch.Tensor:
         """Attention and the output projection on the QKV projection's output ``[b, s, (H + 2 Hkv) D]``."""
         qkv = qkv.view(b, s, self.heads + 2 * self.kv_heads, self.head_dim)
         drop = self.dropout if self.training else 0.0
@@ -85,15 +88,26 @@ class SelfAttention(nn.Module):
             if self.rope is not None:
                 # K14: q and k rotated in one pass into a packed buffer (backward: in place on dQKV)
                 qkv = ops.rope_qkv(qkv.contiguous(), self.rope.cos, self.rope.sin, self.heads + self.kv_heads)
-            o = ops.attention_qkvpacked(qkv, self.heads, self.kv_heads, causal=self.causal, dropout_p=drop)
+            o = ops.attention_qkvpacked(qkv, self.heads, self.kv_heads, causal=self.causal, dropout_p=drop,
+                                        seqlens=seqlens)
             return linear(self.proj, o.view(b, s, self.heads * self.head_dim))
         q, k, v = qkv.split([self.heads, self.kv_heads, self.kv_heads], dim=2)
         q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
         if self.rope is not None:
             q, k = self.rope(q, k)
         gqa = self.kv_heads != self.heads
-        o = F.scaled_dot_product_attention(q, k, v, is_causal=self.causal,
+        mask = valid = None
+        if seqlens is not None:
+            # the same contract as K8's: padded positions replaced by zeros (select), valid rows see the
+            # valid keys, padded rows of the output are zeros (reference.attention)
+            valid = ops.reference.attention_valid(seqlens.to(qkv.device), s)[:, None, :, None]
+            zero = torch.zeros((), dtype=q.dtype, device=q.device)
+            q, k, v = torch.where(valid, q, zero), torch.where(valid, k, zero), torch.where(valid, v, zero)
+            mask = ops.reference.attention_seqlens_mask(seqlens.to(qkv.device), s, self.causal)
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, is_causal=self.causal and mask is None,
                                            dropout_p=self.dropout if self.training else 0.0, enable_gqa=gqa)
+        if valid is not None:
+            o = torch.where(valid, o, torch.zeros((), dtype=o.dtype, device=o.device))
         return linear(self.proj, o.transpose(1, 2).reshape(b, s, self.heads * self.head_dim))
 
 

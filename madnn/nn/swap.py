@@ -12,8 +12,10 @@ kernels as madnn's zoo, not only on the fused optimizer and bucket kernels:
   the ``"madnn_k8"`` attention implementation (HF's ``AttentionInterface``):
   unmasked (or causal-only) bf16 attention with head dim 64/128 runs K8 straight
   from HF's [B, H, S, D] views, attention dropout included (in-kernel mask);
-  padding masks, position biases and decoding fall back to HF's SDPA path, and so
-  does dropout with ``MADNN_ATTN_DROPOUT=0`` or under stream capture.
+  a RIGHT-padded ``attention_mask`` runs K8 too, as per-sequence lengths
+  (:func:`madnn_mask`); any other mask, position biases and decoding fall back to
+  HF's SDPA path, and so does dropout with ``MADNN_ATTN_DROPOUT=0`` or under
+  stream capture.
 
 Every swap keeps parameter and buffer names (state dicts interchange with the
 original model).  The reference had no kernels of its own at all.
@@ -68,16 +70,85 @@ def _swap(model: nn.Module, counts: Dict[str, int]) -> None:
         counts[key] = counts.get(key, 0) + 1
 
 
+_SEQLENS = "_madnn_seqlens"   # by-product attached to the mask tensor: (int32 [B] lengths, causal)
+
+
+def right_padded_lengths(attention_mask: torch.Tensor):
+    """int32 [B] row sums of a 2-D padding mask if every row is ones followed by zeros (right-padded),
+    else None.  One host sync (the comparison's result is read)."""
+    m = attention_mask.to(torch.bool)
+    lens = m.sum(-1)
+    right = m == (torch.arange(m.size(-1), device=m.device)[None, :] < lens[:, None])
+    return lens.to(torch.int32) if bool(right.all()) else None
+
+
+def _has_cross_attention(config) -> bool:
+    """A model whose config can build CROSS-attention masks (encoder-decoder models, decoders with
+    ``add_cross_attention``): HF builds those through the same mask function from the ENCODER's padding
+    mask, and with source and target padded to one length they look like self-attention masks."""
+    return bool(getattr(config, "is_encoder_decoder", False) or getattr(config, "add_cross_attention", False))
+
+
+def _is_cross_attention(module) -> bool:
+    return bool(getattr(module, "is_cross_attention", False)) or "CrossAttention" in type(module).__name__
+
+
+def madnn_mask(batch_size, q_length, kv_length, q_offset=0, kv_offset=0, mask_function=None, attention_mask=None,
+               config=None, **kwargs):
+    """The ``"madnn_k8"`` mask function: HF's ``sdpa_mask``, unchanged, whose result additionally
+    carries the per-sequence lengths when the batch is right-padded self-attention over whole
+    sequences -- a 2-D ``attention_mask``, ``q_length == kv_length``, both offsets 0, the stock causal
+    or bidirectional ``mask_function``, no stream capture in progress (the check below reads a value
+    on the host) and ``attention_mask == (arange < attention_mask.sum(-1))``.  The check costs one host
+    sync per model forward (HF builds the mask once and hands it to every layer), not one per layer.
+    :func:`madnn_attention_forward` runs K8 with ``seqlens`` on such a mask.
+
+    Self-attention only: the kernels take ONE length per sequence for queries and keys alike.  Nothing
+    is attached for a ``config`` (HF hands the model's to the mask function) that can cross-attend
+    (:func:`_has_cross_attention`): the encoder's padding mask, applied to decoder queries of the same
+    padded length, is indistinguishable here from a self-attention mask, and zeroing decoder rows past
+    the SOURCE length would be wrong.  Such models keep SDPA for every masked call."""
+    from transformers.masking_utils import bidirectional_mask_function, causal_mask_function, sdpa_mask
+
+    if mask_function is None:
+        mask_function = causal_mask_function
+    mask = sdpa_mask(batch_size, q_length, kv_length, q_offset, kv_offset, mask_function=mask_function,
+                     attention_mask=attention_mask, config=config, **kwargs)
+    if (not _has_cross_attention(config) and isinstance(mask, torch.Tensor)
+            and isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 2
+            and attention_mask.size(-1) == kv_length and q_length == kv_length
+            and isinstance(q_offset, int) and isinstance(kv_offset, int) and q_offset == 0 and kv_offset == 0
+            and mask_function in (causal_mask_function, bidirectional_mask_function)
+            and not (attention_mask.is_cuda and torch.cuda.is_current_stream_capturing())):
+        lens = right_padded_lengths(attention_mask)
+        if lens is not None:
+            ops._attach(mask, _SEQLENS, (lens, mask_function is causal_mask_function))
+    return mask
+
+
 def madnn_attention_forward(module, query, key, value, attention_mask, dropout: float = 0.0, scaling=None,
                             is_causal=None, position_bias=None, **kwargs):
-    """HF attention-interface entry: K8 for what it supports, HF SDPA for the rest."""
+    """HF attention-interface entry: K8 for what it supports, HF SDPA for the rest.
+
+    A mask that carries lengths (:func:`madnn_mask`: a right-padded batch) runs K8 with ``seqlens``.
+    K8 then returns ZEROS at the padded query rows where SDPA returns values (there a padded query
+    still attends to the valid keys); the valid positions, and therefore any loss that ignores the
+    pads (labels of -100), are unaffected.  Any other non-null mask runs SDPA, and so does a
+    cross-attention module whatever its mask carries (key lengths are not query lengths there)."""
     is_causal = is_causal if is_causal is not None else getattr(module, "is_causal", True)
     q_len, kv_len = query.shape[2], key.shape[2]
-    if (attention_mask is None and position_bias is None and q_len == kv_len
+    lens = ops._attached(attention_mask, _SEQLENS) if isinstance(attention_mask, torch.Tensor) else None
+    if lens is not None and _is_cross_attention(module):
+        lens = None
+    if ((attention_mask is None or lens is not None) and position_bias is None and q_len == kv_len
             and not kwargs.get("output_attentions", False)
             and ops.attention_supported(query, query.shape[-1], dropout) and key.dtype == query.dtype):
+        if lens is not None:   # the mask holds the causal structure itself (HF passes is_causal=False with it)
+            seqlens, causal = lens
+        else:
+            seqlens, causal = None, bool(is_causal and q_len > 1)
         o = ops.attention(query.transpose(1, 2), key.transpose(1, 2), value.transpose(1, 2),
-                          causal=bool(is_causal and q_len > 1), scale=scaling, dropout_p=dropout)
+                          causal=causal, scale=scaling, dropout_p=dropout, seqlens=seqlens)
         _stats["k8"] += 1
         return o, None
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
@@ -100,11 +171,11 @@ def register_hf_attention() -> bool:
         return True
     try:
         from transformers import AttentionInterface
-        from transformers.masking_utils import AttentionMaskInterface, sdpa_mask
+        from transformers.masking_utils import AttentionMaskInterface
     except Exception:  # noqa: BLE001 - transformers absent or too old: nothing to route
         return False
     AttentionInterface.register(ATTN_IMPL, madnn_attention_forward)
-    AttentionMaskInterface.register(ATTN_IMPL, sdpa_mask)
+    AttentionMaskInterface.register(ATTN_IMPL, madnn_mask)
     _registered["done"] = True
     return True
 

@@ -665,19 +665,20 @@ class _AttnFn(torch.autograd.Function):
     """q [B,S,H,D], k/v [B,S,Hkv,D] (strided views) -> o [B,S,H,D] contiguous."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, p=0.0, seed=0, offset=0):
-        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset)
-        ctx.save_for_backward(q, k, v, o, lse)
+    def forward(ctx, q, k, v, causal, scale, p=0.0, seed=0, offset=0, seqlens=None):
+        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset, seqlens)
+        ctx.save_for_backward(q, k, v, o, lse, seqlens)   # seqlens (or None) stays on the device: no host sync
         ctx.causal, ctx.scale = causal, scale
         ctx.drop = (p, seed, offset)   # the backward kernels regenerate the mask from these
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, seqlens = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, float(ctx.scale), None, *ctx.drop)
-        return dq, dk, dv, None, None, None, None, None
+        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, float(ctx.scale), None, *ctx.drop,
+                                 seqlens)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 class _AttnPackedFn(torch.autograd.Function):
@@ -685,10 +686,10 @@ class _AttnPackedFn(torch.autograd.Function):
     into one buffer (no split/cat copies in either direction)."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, kv_heads, causal, scale, p=0.0, seed=0, offset=0):
+    def forward(ctx, qkv, heads, kv_heads, causal, scale, p=0.0, seed=0, offset=0, seqlens=None):
         q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
-        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset)
-        ctx.save_for_backward(qkv, o, lse)
+        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset, seqlens)
+        ctx.save_for_backward(qkv, o, lse, seqlens)
         ctx.meta = (heads, kv_heads, bool(causal), float(scale))
         ctx.drop = (p, seed, offset)
         # qkv is (a view of) a biased madnn Linear's output: the backward kernels also sum dQKV's
@@ -699,7 +700,7 @@ class _AttnPackedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, seqlens = ctx.saved_tensors
         heads, kv_heads, causal, scale = ctx.meta
         q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
         dqkv = torch.empty_like(qkv)
@@ -707,10 +708,10 @@ class _AttnPackedFn(torch.autograd.Function):
         cs = None
         if ctx.colsum:
             cs = torch.empty((heads + 2 * kv_heads) * qkv.size(-1), dtype=ctx.colsum_dtype, device=qkv.device)
-        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cs, *ctx.drop)
+        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cs, *ctx.drop, seqlens)
         if cs is not None:
             _attach(dqkv, "_madnn_colsum", cs)
-        return dqkv, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None
 
 
 ATTN_COLSUM = os.environ.get("MADNN_ATTN_COLSUM", "1") != "0"  # A/B switch (see _AttnPackedFn.forward)
@@ -756,32 +757,56 @@ def _attn_scale_ok(scale: float) -> bool:
     return math.isfinite(scale) and scale > 0
 
 
-def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dropout_p: float = 0.0, rng=None):
+def _seqlens_arg(seqlens, like: torch.Tensor):
+    """``seqlens`` as the kernels take it: None, or a contiguous int32 [B] tensor on ``like``'s device
+    (an integer tensor of another dtype or device is converted; values are never read on the host)."""
+    if seqlens is None:
+        return None
+    if seqlens.dim() != 1 or seqlens.size(0) != like.size(0) or seqlens.is_floating_point():
+        raise ValueError(f"seqlens must be an integer [B = {like.size(0)}] tensor, got {tuple(seqlens.shape)} "
+                         f"{seqlens.dtype}")
+    return seqlens.to(device=like.device, dtype=torch.int32).contiguous()
+
+
+def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dropout_p: float = 0.0, rng=None,
+              seqlens=None):
     """Scaled-dot-product attention on [B, S, heads, D] tensors (GQA when k/v have fewer heads).
     Returns [B, S, H, D].  HIP bf16 inputs run K8; anything else runs SDPA.  ``dropout_p`` drops
     attention probabilities (K8: in-kernel mask, see :func:`reference.attention_dropout_mask`);
     ``rng = (seed, offset)`` pins K8's mask, by default it is drawn from torch's device generator.
     K8 takes a finite positive ``scale`` only (its kernels refuse any other: they mask with
-    infinities before scaling); a zero, negative or non-finite scale runs :func:`reference.attention`."""
+    infinities before scaling); a zero, negative or non-finite scale runs :func:`reference.attention`.
+
+    ``seqlens`` (int32 [B], on the inputs' device) declares a right-padded batch: sequence ``b`` has
+    ``L_b = clamp(seqlens[b], 0, S)`` valid tokens followed by padding (the clamp is the kernels': no
+    host sync, so the call stays graph-capturable).  A valid query row ``q < L_b`` attends to the keys
+    ``k < L_b`` (and ``k <= q`` when causal), as if sequence ``b`` ran alone at length ``L_b``.  Padded
+    query rows of the output are exact zeros and so are the gradients at padded positions of q, k and
+    v; nothing stored at a padded position of q, k, v or the incoming gradient reaches a result (NaN
+    there does not propagate).  K8 skips the key tiles and query blocks past ``L_b``.  The dropout
+    mask stays the same function of the absolute (b, h, q, k).  ``seqlens=None``: every position valid."""
     scale = scale if scale is not None else q.size(-1) ** -0.5
+    seqlens = _seqlens_arg(seqlens, q)
     if attention_supported(q, q.size(-1), dropout_p) and _attn_scale_ok(scale):
         _need_native("attention")
-        return _AttnFn.apply(q, k, v, causal, scale, *_dropout_args(q, dropout_p, rng))
-    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p)
+        return _AttnFn.apply(q, k, v, causal, scale, *_dropout_args(q, dropout_p, rng), seqlens)
+    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p, seqlens=seqlens)
 
 
 def attention_qkvpacked(qkv, heads: int, kv_heads: int, *, causal: bool = True, scale: Optional[float] = None,
-                        dropout_p: float = 0.0, rng=None):
+                        dropout_p: float = 0.0, rng=None, seqlens=None):
     """Attention straight from a packed projection ``qkv`` [B, S, heads + 2*kv_heads, D]
-    (``dropout_p`` / ``rng`` as in :func:`attention`; a ``scale`` that is not finite and positive runs
-    :func:`reference.attention`, as there)."""
+    (``dropout_p`` / ``rng`` / ``seqlens`` as in :func:`attention`; a ``scale`` that is not finite and
+    positive runs :func:`reference.attention`, as there).  With ``seqlens`` the column sums handed to a
+    biased projection as its bias gradient cover the valid rows only (the padded rows of dQKV are zeros)."""
     d = qkv.size(-1)
     scale = scale if scale is not None else d ** -0.5
+    seqlens = _seqlens_arg(seqlens, qkv)
     if attention_supported(qkv, d, dropout_p) and qkv.is_contiguous() and _attn_scale_ok(scale):
         _need_native("attention")
-        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_dropout_args(qkv, dropout_p, rng))
+        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_dropout_args(qkv, dropout_p, rng), seqlens)
     q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
-    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p)
+    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p, seqlens=seqlens)
 
 
 # ---------------------------------------------------------------- K14 / K15

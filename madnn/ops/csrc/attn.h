@@ -40,6 +40,10 @@ struct MadnnAttnArgs {
   float drop_rp;
   uint64_t drop_seed;
   uint64_t drop_offset;
+  // right-padded batches (attn.hip header, "Per-sequence lengths"): int32 [B], sequence b has
+  // clamp(seqlens[b], 0, S) valid tokens followed by padding; null = every position valid (the dense
+  // kernels).  Last field: the offsets above are those of the struct without it.
+  const int32_t* seqlens;
 };
 
 }

@@ -52,6 +52,21 @@
 //    start at zero (the -delta start of ACCD would be masked along with dPraw).
 // madnn.ops.reference.attention_dropout_mask is the host mirror (bit-identical);
 // attn_dropout_mask_kernel writes the mask out through the same drop_block() for tests.
+//
+// Per-sequence lengths (the VARLEN instantiations of the three register-staged kernels; the LDS-DMA
+// ring kernels, whose counted waits assume whole tiles, are not taken with them).  A right-padded
+// batch: sequence b has L = clamp(seqlens[b], 0, S) valid tokens, then padding.  a.S keeps its role
+// as the LAYOUT (grid decomposition, lse / delta / cpart row strides, address clamps -- a clamp to
+// L - 1 would read row -1 at L = 0); VALIDITY moves to the wave-uniform L (seq_len(), an SGPR):
+//  * the key loop ends at L (forward, dQ) and the query-tile loop at L (dK/dV): the tiles past L are
+//    never loaded or computed (what that saves in time: docs/PERF.md, round 15);
+//  * rows at or past L never reach a result: staged tiles end at L (zeros from the bounded loads),
+//    per-lane operand rows (Q, dO, O; K, V) are replaced by zeros with a select, never multiplied away;
+//  * padded query rows get o = 0, lse = 0, dq = 0, delta = 0, padded keys dk = dv = 0 (exact zeros,
+//    by a select at the store), so the column sums cover valid rows only;
+//  * a workgroup whose 128 rows all lie at or past L writes those zeros (and its zero cpart row: the
+//    finalize sums every row) and returns before any tile work;
+//  * the dropout mask stays the same function of the absolute (b, h, q, k).
 #include <type_traits>
 
 #include "attn.h"
@@ -147,6 +162,28 @@ __device__ __forceinline__ void map_block(int nblk, int heads, bool heavy_last, 
   if (heavy_last) blk = nblk - 1 - blk;  // causal: the longest query blocks start first
   b = bh / heads;
   h = bh % heads;
+}
+
+// Valid length of sequence b: S without VARLEN, else seqlens[b] clamped into [0, S].  b comes from
+// the workgroup id, so the load is scalar and L lives in an SGPR.  (Scalars, not the argument block by
+// reference: a reference to the by-value kernel argument changed the dense kernels' schedules.)
+template <bool VARLEN>
+__device__ __forceinline__ int seq_len(const int32_t* seqlens, int b, int S) {
+  if constexpr (VARLEN) {
+    return min(max(__builtin_amdgcn_readfirstlane(seqlens[b]), 0), S);
+  } else {
+    return S;
+  }
+}
+
+// One [D] row of zeros at row `row` of a [.., heads, D] output (a padded position)
+template <int D>
+__device__ __forceinline__ void store_zero_row(uint16_t* rowp, int hh) {
+#pragma unroll
+  for (int d = 0; d < D / 32; ++d) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) store4_bf16(rowp + d * 32 + 8 * g + 4 * hh, 0.f, 0.f, 0.f, 0.f);
+  }
 }
 
 // ------------------------------------------------------------------ dropout mask
@@ -251,9 +288,12 @@ __device__ __forceinline__ void softmax_tile(f32x16 (&sc)[2], f32x16 (&o)[DB], f
 
 // D = 128 is built for 2 waves per SIMD (256 VGPRs, a few spills; 348 and one wave unbounded):
 // +27 % at Llama-3 8B's shape, profiles/r5_attn_ab_occupancy.json
-template <int D, bool CAUSAL, bool DROP = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
 __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(const MadnnAttnArgs a) {
   constexpr int DS = D / 16, DB = D / 32;
+  // VARLEN at D = 128: ONE staging tuple, the next K tile held during the scores, the next V tile during
+  // the P.V products (16 VGPRs fewer than K and V together: no spills under the 2-wave bound)
+  constexpr bool ONESTAGE = VARLEN && D == 128;
   __shared__ __attribute__((aligned(16))) uint16_t sK[2][kTile * D];
   __shared__ __attribute__((aligned(16))) uint16_t sV[2][kTile * D];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
@@ -263,6 +303,16 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
   const int hk = h / (a.H / a.Hkv);
   const int q0w = qblk * kRowsWG + wave * 32;
   const int qrow = q0w + l32;
+  const int L = seq_len<VARLEN>(a.seqlens, b, a.S);  // valid rows / keys of this sequence (a.S without VARLEN)
+  if constexpr (VARLEN) {
+    if (qblk * kRowsWG >= L) {  // every row of the workgroup is padding: o = 0, lse = 0, no tile work
+      if (qrow < a.S) {
+        store_zero_row<D>(a.o + b * a.o_sb + h * a.o_sh + (int64_t)qrow * a.o_ss, hh);
+        if (hh == 0) a.lse[((int64_t)b * a.H + h) * a.S + qrow] = 0.f;
+      }
+      return;
+    }
+  }
 
   // -c Q^T as the B operand of S^T = K.Q^T: lane holds -c Q[qrow][16s + 8hh + j]
   bf16x8 qf[DS];
@@ -270,6 +320,10 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
     const uint16_t* qp = a.q + b * a.q_sb + h * a.q_sh + (int64_t)min(qrow, a.S - 1) * a.q_ss;
 #pragma unroll
     for (int s = 0; s < DS; ++s) qf[s] = scale_bf16x8(*reinterpret_cast<const bf16x8*>(qp + 16 * s + 8 * hh), -a.scale_log2);
+    if constexpr (VARLEN) {  // a padded row's values (NaN included) are replaced, not multiplied away
+#pragma unroll
+      for (int s = 0; s < DS; ++s) qf[s] = qrow < L ? qf[s] : __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+    }
   }
   const uint16_t* kb_ = a.k + b * a.k_sb + hk * a.k_sh;
   const uint16_t* vb_ = a.v + b * a.v_sb + hk * a.v_sh;
@@ -278,24 +332,33 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
   for (int d = 0; d < DB; ++d) o[d] = zero16();
   float m = kNegBig, mi = 0.f, l = 0.f;
   f32x16 mref = zero16();
-  const int kv_end = CAUSAL ? min(a.S, qblk * kRowsWG + kRowsWG) : a.S;
+  const int kv_end = CAUSAL ? min(L, qblk * kRowsWG + kRowsWG) : L;
   const int ntiles = (kv_end + kTile - 1) / kTile;
 
-  TileStage<D> stk, stv;  // global loads (see TileStage)
-  stk.load(kb_, a.k_ss, 0, a.S, tid);
-  stv.load(vb_, a.v_ss, 0, a.S, tid);
-  stk.store(sK[0], tid);
-  stv.store(sV[0], tid);
+  // global loads (see TileStage); ONESTAGE: stk alone, K then V, through buffer loads bounded at row L (no
+  // per-lane 64-bit addresses, branches or zero fills: with them the full-attention kernel still spilled)
+  TileStage<D, ONESTAGE> stk, stv;
+  stk.load(kb_, a.k_ss, 0, L, tid);
+  if constexpr (ONESTAGE) {
+    stk.store(sK[0], tid);
+    stk.load(vb_, a.v_ss, 0, L, tid);
+    stk.store(sV[0], tid);
+  } else {
+    stv.load(vb_, a.v_ss, 0, L, tid);
+    stk.store(sK[0], tid);
+    stv.store(sV[0], tid);
+  }
   __syncthreads();
   for (int t = 0; t < ntiles; ++t) {
     const int cur = t & 1;
     const bool more = t + 1 < ntiles;
     if (more) {
-      stk.load(kb_, a.k_ss, (t + 1) * kTile, a.S, tid);
-      stv.load(vb_, a.v_ss, (t + 1) * kTile, a.S, tid);
+      stk.load(kb_, a.k_ss, (t + 1) * kTile, L, tid);
+      if constexpr (!ONESTAGE) stv.load(vb_, a.v_ss, (t + 1) * kTile, L, tid);
     }
     const int k0 = t * kTile;
-    if (!CAUSAL || k0 <= q0w + 31) {
+    // VARLEN: a wave whose 32 rows are all padding only stages tiles
+    if ((!CAUSAL || k0 <= q0w + 31) && (!VARLEN || q0w < L)) {
       f32x16 sc[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -303,10 +366,10 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
 #pragma unroll
         for (int s = 0; s < DS; ++s) sc[kb] = mfma(lds_row<D>(sK[cur], kb * 32 + l32, 2 * s + hh), qf[s], sc[kb]);
       }
-      if ((k0 + kTile > a.S) || (CAUSAL && k0 + kTile - 1 > q0w)) {
+      if ((k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w)) {
         // key k0 + kb*32 + acc_row(r, hh) is valid iff its compile-time offset kb*32 + acc_row(r, 0)
         // <= lim (one compare + select per element)
-        const int lim = (CAUSAL ? min(a.S - 1, qrow) : a.S - 1) - k0 - 4 * hh;
+        const int lim = (CAUSAL ? min(L - 1, qrow) : L - 1) - k0 - 4 * hh;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
@@ -323,6 +386,12 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
           });
         }
       }
+      if constexpr (ONESTAGE) {  // between the scores and P.V: next K -> LDS, next V -> registers
+        if (more) {
+          stk.store(sK[cur ^ 1], tid);
+          stk.load(vb_, a.v_ss, (t + 1) * kTile, L, tid);
+        }
+      }
       // O^T[d][q] += sum_key V[key][d] P^T[key][q]
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -333,10 +402,19 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
           for (int d = 0; d < DB; ++d) o[d] = mfma(lds_col_acc<D>(sV[cur], kb * 32 + 16 * s, d * 32, lane), pf, o[d]);
         }
       }
+    } else if constexpr (ONESTAGE) {  // a wave that computes nothing stages all the same
+      if (more) {
+        stk.store(sK[cur ^ 1], tid);
+        stk.load(vb_, a.v_ss, (t + 1) * kTile, L, tid);
+      }
     }
     if (more) {
-      stk.store(sK[cur ^ 1], tid);
-      stv.store(sV[cur ^ 1], tid);
+      if constexpr (ONESTAGE) {
+        stk.store(sV[cur ^ 1], tid);
+      } else {
+        stk.store(sK[cur ^ 1], tid);
+        stv.store(sV[cur ^ 1], tid);
+      }
     }
     __syncthreads();
   }
@@ -345,6 +423,15 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
   if constexpr (DROP) inv *= a.drop_rp;
   if (qrow < a.S) {
     uint16_t* op = a.o + b * a.o_sb + h * a.o_sh + (int64_t)qrow * a.o_ss;
+    if constexpr (VARLEN) {  // a padded row of a block with valid rows: exact zeros, lse = 0
+      const bool pad = qrow >= L;
+#pragma unroll
+      for (int d = 0; d < DB; ++d) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[d][r] = pad ? 0.f : o[d][r];
+      }
+      inv = pad ? 0.f : inv;
+    }
 #pragma unroll
     for (int d = 0; d < DB; ++d) {
 #pragma unroll
@@ -353,7 +440,7 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
                     o[d][4 * g + 3] * inv);
       }
     }
-    if (hh == 0) a.lse[((int64_t)b * a.H + h) * a.S + qrow] = m + log2f(lt);
+    if (hh == 0) a.lse[((int64_t)b * a.H + h) * a.S + qrow] = VARLEN && qrow >= L ? 0.f : m + log2f(lt);
   }
 }
 
@@ -369,16 +456,20 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
 // at D = 64 the 2-wave build measured neutral).
 // DROP: dS = P (rp M dPraw - delta): the mask and rp go onto the raw dP before the subtraction, so the
 // dP accumulators start at zero at D = 64 too (no ACCD).
-template <int D, bool CAUSAL, bool DROP = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
 __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel(const MadnnAttnArgs a) {
   constexpr int DS = D / 16, DB = D / 32;
   constexpr bool ACCD = D == 64 && !DROP, KSPLIT = D == 128;
+  // VARLEN at D = 128: ONE staging tuple, the next K tile held during the first 32-key half, the next V
+  // tile during the second (16 VGPRs fewer than K and V together: no spills under the 2-wave bound)
+  constexpr bool ONESTAGE = VARLEN && D == 128;
   // K and V stages in one block: after the loop the column-sum epilogue reuses all of it as a
   // [128 rows][D] fp32 image (4 * 64 * D bf16 = 128 * D fp32)
   __shared__ __attribute__((aligned(16))) uint16_t sKV[4][kTile * D];
   uint16_t(*sK)[kTile * D] = sKV;
   uint16_t(*sV)[kTile * D] = sKV + 2;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
+  const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
+  const int wave = VARLEN ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int nqb = (a.S + kRowsWG - 1) / kRowsWG;
   int qblk, b, h;
   map_block(nqb, a.H, CAUSAL, qblk, b, h);
@@ -386,6 +477,20 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
   const int q0w = qblk * kRowsWG + wave * 32;
   const int qrow = q0w + l32;
   const int qc = min(qrow, a.S - 1);
+  const int L = seq_len<VARLEN>(a.seqlens, b, a.S);  // valid rows / keys of this sequence (a.S without VARLEN)
+  if constexpr (VARLEN) {
+    if (qblk * kRowsWG >= L) {  // every row of the workgroup is padding: dq = 0, delta = 0, a zero cpart row
+      if (qrow < a.S) {
+        store_zero_row<D>(a.dq + b * a.dq_sb + h * a.dq_sh + (int64_t)qrow * a.dq_ss, hh);
+        if (hh == 0) a.delta[((int64_t)b * a.H + h) * a.S + qrow] = 0.f;
+      }
+      if (a.cpart != nullptr && tid < D) {
+        const int64_t C = (int64_t)(a.H + 2 * a.Hkv) * D;
+        a.cpart[((int64_t)b * nqb + qblk) * C + (int64_t)h * D + tid] = 0.f;
+      }
+      return;
+    }
+  }
   bf16x8 qf[DS], df[DS];
   // delta = rowsum(dO * O) of this lane's query row, from the dO fragments it holds anyway plus the
   // matching O halves (the two lane halves hh = 0/1 own alternate 8-column chunks); written out for
@@ -404,9 +509,19 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
       for (int j = 0; j < 8; ++j) dl = fmaf(static_cast<float>(df[s][j]), static_cast<float>(ov[j]), dl);
     }
     dl += __shfl_xor(dl, 32, kWave);
+    if constexpr (VARLEN) {  // a padded row: Q, dO and the dO * O products are replaced by zeros (select)
+      const bool pad = qrow >= L;
+#pragma unroll
+      for (int s = 0; s < DS; ++s) {
+        qf[s] = pad ? __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u}) : qf[s];
+        df[s] = pad ? __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u}) : df[s];
+      }
+      dl = pad ? 0.f : dl;
+    }
   }
   const int64_t srow = ((int64_t)b * a.H + h) * a.S + qc;
-  const float lse = a.lse[srow];
+  float lse = a.lse[srow];
+  if constexpr (VARLEN) lse = qrow < L ? lse : 0.f;
   const f32x16 lse16 = splat16(lse);
   if (hh == 0 && qrow < a.S) a.delta[srow] = dl;
   const uint16_t* kb_ = a.k + b * a.k_sb + hk * a.k_sh;
@@ -417,27 +532,44 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
   f32x16 ndl;
 #pragma unroll
   for (int r = 0; r < 16; ++r) ndl[r] = -dl;
-  const int kv_end = CAUSAL ? min(a.S, qblk * kRowsWG + kRowsWG) : a.S;
+  const int kv_end = CAUSAL ? min(L, qblk * kRowsWG + kRowsWG) : L;
   const int ntiles = (kv_end + kTile - 1) / kTile;
-  TileStage<D, true> stk, stv;
-  stk.load(kb_, a.k_ss, 0, a.S, tid);
-  stv.load(vb_, a.v_ss, 0, a.S, tid);
-  stk.store(sK[0], tid);
-  stv.store(sV[0], tid);
+  TileStage<D, true> stk, stv;  // ONESTAGE: stk alone, K then V
+  stk.load(kb_, a.k_ss, 0, L, tid);
+  if constexpr (ONESTAGE) {
+    stk.store(sK[0], tid);
+    stk.load(vb_, a.v_ss, 0, L, tid);
+    stk.store(sV[0], tid);
+  } else {
+    stv.load(vb_, a.v_ss, 0, L, tid);
+    stk.store(sK[0], tid);
+    stv.store(sV[0], tid);
+  }
   __syncthreads();
   int t = 0;
   auto tile = [&](auto curc) {
     constexpr int cur = decltype(curc)::value;
     const bool more = t + 1 < ntiles;
     if (more) {
-      stk.load(kb_, a.k_ss, (t + 1) * kTile, a.S, tid);
-      stv.load(vb_, a.v_ss, (t + 1) * kTile, a.S, tid);
+      stk.load(kb_, a.k_ss, (t + 1) * kTile, L, tid);
+      if constexpr (!ONESTAGE) stv.load(vb_, a.v_ss, (t + 1) * kTile, L, tid);
     }
+    // ONESTAGE, between the two halves (every wave, computing or not): next K -> LDS, next V -> registers
+    auto k_out_v_in = [&]() {
+      if constexpr (ONESTAGE) {
+        if (more) {
+          stk.store(sK[cur ^ 1], tid);
+          stk.load(vb_, a.v_ss, (t + 1) * kTile, L, tid);
+        }
+      }
+    };
     const int k0 = t * kTile;
-    if (KSPLIT && (!CAUSAL || k0 <= q0w + 31)) {
+    // VARLEN: a wave whose 32 rows are all padding only stages tiles
+    const bool live = (!CAUSAL || k0 <= q0w + 31) && (!VARLEN || q0w < L);
+    if (KSPLIT && live) {
       // one 32-key half at a time: S, dP, dS and its dQ products, so only one half's accumulators live
-      const bool edge = (k0 + kTile > a.S) || (CAUSAL && k0 + kTile - 1 > q0w);
-      const int lim = (CAUSAL ? min(qrow, a.S - 1) : a.S - 1) - k0 - 4 * hh;
+      const bool edge = (k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w);
+      const int lim = (CAUSAL ? min(qrow, L - 1) : L - 1) - k0 - 4 * hh;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         f32x16 sc = zero16(), dp = zero16();
@@ -462,8 +594,9 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
 #pragma unroll
           for (int d = 0; d < DB; ++d) dq[d] = mfma(lds_col_acc<D>(sK[cur], kb * 32 + 16 * s, d * 32, lane), sf, dq[d]);
         }
+        if (kb == 0) k_out_v_in();
       }
-    } else if (!CAUSAL || k0 <= q0w + 31) {
+    } else if (live) {
       f32x16 sc[2], dp[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -477,10 +610,10 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
       }
       // masking as one wave-uniform block on the scores (exp2(-inf) = 0): interior tiles run
       // none of it (a per-element `if` costs an exec-mask branch per element)
-      if ((k0 + kTile > a.S) || (CAUSAL && k0 + kTile - 1 > q0w)) {
+      if ((k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w)) {
         // key = k0 + off + 4 hh with off = kb*32 + acc_row(r, 0) a compile-time constant: the mask is
         // one compare of that constant against a per-lane limit (acc = +inf: p = 0)
-        const int lim = (CAUSAL ? min(qrow, a.S - 1) : a.S - 1) - k0 - 4 * hh;
+        const int lim = (CAUSAL ? min(qrow, L - 1) : L - 1) - k0 - 4 * hh;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
@@ -515,7 +648,10 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
         }
       }
     }
-    if (more) {
+    if constexpr (ONESTAGE) {
+      if (!live) k_out_v_in();
+      if (more) stk.store(sV[cur ^ 1], tid);
+    } else if (more) {
       stk.store(sK[cur ^ 1], tid);
       stv.store(sV[cur ^ 1], tid);
     }
@@ -527,6 +663,14 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
     tile(std::integral_constant<int, 1>{});
   }
   if (t < ntiles) tile(std::integral_constant<int, 0>{});
+  if constexpr (VARLEN) {  // a padded row of a block with valid rows: exact zeros (and in the column sums)
+    const bool pad = qrow >= L;
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dq[d][r] = pad ? 0.f : dq[d][r];
+    }
+  }
   if (qrow < a.S) {
     uint16_t* qp = a.dq + b * a.dq_sb + h * a.dq_sh + (int64_t)qrow * a.dq_ss;
     const float sc = a.scale;
@@ -950,10 +1094,13 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_dma_kernel(const MadnnAttnA
 // same dS = P (rp M dPraw - delta) as dQ (no ACCD).  At D = 64 it is bounded to 2 waves per SIMD (256 VGPRs,
 // no spill; 264 and one wave unbounded): forward + backward -16 % / -13 % at the GPT-2 medium / BERT-large
 // shapes (docs/PERF.md, round 11).
-template <int D, bool CAUSAL, bool DROP = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
 __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dkdv_kernel(const MadnnAttnArgs a) {
   constexpr int DS = D / 16, DB = D / 32;
   constexpr bool ACCD = D == 64 && !DROP;
+  // VARLEN with dropout at D = 64: ONE staging tuple, the next Q tile held during the S / dP products,
+  // the next dO tile during the rest (8 VGPRs fewer than Q and dO together: no spills under the 2-wave bound)
+  constexpr bool ONESTAGE = VARLEN && DROP && D == 64;
   __shared__ __attribute__((aligned(16))) uint16_t sQ[2][kTile * D];
   __shared__ __attribute__((aligned(16))) uint16_t sO[2][kTile * D];  // dO
   __shared__ float sL[2][kTile], sD[2][kTile];
@@ -965,6 +1112,28 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
   const int k0w = kblk * kRowsWG + wave * 32;
   const int krow = k0w + l32;
   const int kc = min(krow, a.S - 1);
+  const int L = seq_len<VARLEN>(a.seqlens, b, a.S);  // valid rows / keys of this sequence (a.S without VARLEN)
+  if constexpr (VARLEN) {
+    if (kblk * kRowsWG >= L) {  // every key of the workgroup is padding: dk = dv = 0, zero cpart columns
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = k0w + acc_row(r, hh);
+        if (key < a.S) {
+#pragma unroll
+          for (int d = 0; d < DB; ++d) {
+            (a.dk + b * a.dk_sb + hk * a.dk_sh)[(int64_t)key * a.dk_ss + d * 32 + l32] = 0;
+            (a.dv + b * a.dv_sb + hk * a.dv_sh)[(int64_t)key * a.dv_ss + d * 32 + l32] = 0;
+          }
+        }
+      }
+      if (a.cpart != nullptr && tid < 2 * D) {
+        const int64_t C = (int64_t)(a.H + 2 * a.Hkv) * D;
+        const int64_t col = (int64_t)a.H * D + (tid < D ? (int64_t)hk * D + tid : (int64_t)(a.Hkv + hk) * D + tid - D);
+        a.cpart[((int64_t)b * nkb + kblk) * C + col] = 0.f;
+      }
+      return;
+    }
+  }
   // K^T / V^T as the B operand of S = Q.K^T / dP = dO.V^T: lane holds K[krow][16s + 8hh + j]
   bf16x8 kf[DS], vf[DS];
   {
@@ -975,6 +1144,13 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
       kf[s] = *reinterpret_cast<const bf16x8*>(kp + 16 * s + 8 * hh);
       vf[s] = *reinterpret_cast<const bf16x8*>(vp + 16 * s + 8 * hh);
     }
+    if constexpr (VARLEN) {  // a padded key's K / V rows are replaced by zeros (its dk / dv are not stored)
+#pragma unroll
+      for (int s = 0; s < DS; ++s) {
+        kf[s] = krow < L ? kf[s] : __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+        vf[s] = krow < L ? vf[s] : __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+      }
+    }
   }
   f32x16 dk[DB], dv[DB];
 #pragma unroll
@@ -983,7 +1159,7 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
     dv[d] = zero16();
   }
   const int t0 = CAUSAL ? (kblk * kRowsWG) / kTile : 0;
-  const int nt = (a.S + kTile - 1) / kTile - t0;
+  const int nt = (L + kTile - 1) / kTile - t0;  // query tiles with a valid row
   const int total = G * nt;
   // tile `it` = (query head hk*G + it / nt, query tile t0 + it % nt); the loop walks it with two
   // counters instead of a per-tile integer division
@@ -998,14 +1174,15 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
   // latency is covered by the tile's compute (a load stored right away exposes it every tile)
   // (one buffer load per lane of waves 0 / 1 through a descriptor that ends at row S: a row past the
   // end reads 0 for both -- harmless, since its Q and dO rows are zeros, so its P and dS terms
-  // multiply zero operands)
+  // multiply zero operands; VARLEN: the descriptors of the statistics and of the Q / dO tiles end at
+  // row L, so the same holds for the padded query rows)
   const int swave = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform to the compiler
   auto fetch_stats = [&](int hq, int q0) -> float {
     float v = 0.f;
     if (swave < 2) {
       const float* arr = (swave == 0 ? a.lse : a.delta) + ((int64_t)b * a.H + hq) * a.S + q0;
       const __amdgpu_buffer_rsrc_t rsrc =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(arr), 0, max(a.S - q0, 0) * 4, 0x00020000);
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(arr), 0, max(L - q0, 0) * 4, 0x00020000);
       v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, lane * 4, 0, 0));
       if (ACCD && swave == 1) v = -v;
     }
@@ -1023,10 +1200,16 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
     const uint16_t *qp, *dp;
     int q0, hq;
     src(0, 0, qp, dp, q0, hq);
-    stq.load(qp, a.q_ss, q0, a.S, tid);
-    sto.load(dp, a.o_ss, q0, a.S, tid);
-    stq.store(sQ[0], tid);
-    sto.store(sO[0], tid);
+    stq.load(qp, a.q_ss, q0, L, tid);
+    if constexpr (ONESTAGE) {
+      stq.store(sQ[0], tid);
+      stq.load(dp, a.o_ss, q0, L, tid);
+      stq.store(sO[0], tid);
+    } else {
+      sto.load(dp, a.o_ss, q0, L, tid);
+      stq.store(sQ[0], tid);
+      sto.store(sO[0], tid);
+    }
     put_stats(fetch_stats(hq, q0), 0);
   }
   __syncthreads();
@@ -1042,13 +1225,22 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
       nxt_t = 0;
       ++nxt_h;
     }
+    // ONESTAGE, once the S / dP products have read this tile (every wave, computing or not): the next
+    // Q tile -> LDS, the next dO tile -> the same registers
+    auto q_out_do_in = [&]() {
+      const uint16_t *qp, *dp;
+      int q0n, hqn;
+      src(nxt_h, nxt_t, qp, dp, q0n, hqn);
+      stq.store(sQ[cur ^ 1], tid);
+      stq.load(dp, a.o_ss, q0n, L, tid);
+    };
     float stat_next = 0.f;
     if (more) {
       const uint16_t *qp, *dp;
       int q0n, hqn;
       src(nxt_h, nxt_t, qp, dp, q0n, hqn);
-      stq.load(qp, a.q_ss, q0n, a.S, tid);
-      sto.load(dp, a.o_ss, q0n, a.S, tid);
+      stq.load(qp, a.q_ss, q0n, L, tid);
+      if constexpr (!ONESTAGE) sto.load(dp, a.o_ss, q0n, L, tid);
       stat_next = fetch_stats(hqn, q0n);
     }
     const int q0 = (t0 + cur_t) * kTile;
@@ -1071,6 +1263,9 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
           sc[qb] = mfma(lds_row<D>(sQ[cur], qb * 32 + l32, 2 * s + hh), kf[s], sc[qb]);
           dp[qb] = mfma(lds_row<D>(sO[cur], qb * 32 + l32, 2 * s + hh), vf[s], dp[qb]);
         }
+      }
+      if constexpr (ONESTAGE) {  // after the S / dP products: next Q -> LDS, next dO -> registers
+        if (more) q_out_do_in();
       }
       if (CAUSAL && q0 < k0w + 31) {  // diagonal tile: one wave-uniform masking block
         const int lo = krow - q0 - 4 * hh;  // query offset qb*32 + acc_row(r, 0) must reach it
@@ -1119,7 +1314,13 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
         }
       }
     }
-    if (more) {
+    if constexpr (ONESTAGE) {
+      if (more) {
+        if (CAUSAL && q0 + kTile - 1 < k0w) q_out_do_in();  // a wave that computed nothing
+        stq.store(sO[cur ^ 1], tid);
+        put_stats(stat_next, cur ^ 1);
+      }
+    } else if (more) {
       stq.store(sQ[cur ^ 1], tid);
       sto.store(sO[cur ^ 1], tid);
       put_stats(stat_next, cur ^ 1);
@@ -1144,7 +1345,11 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
     if (key < a.S) {
 #pragma unroll
       for (int d = 0; d < DB; ++d) {
-        const unsigned short kb16 = f32_to_bf16(dk[d][r] * a.scale), vb16 = f32_to_bf16(dv[d][r]);
+        unsigned short kb16 = f32_to_bf16(dk[d][r] * a.scale), vb16 = f32_to_bf16(dv[d][r]);
+        if constexpr (VARLEN) {  // a padded key of a block with valid keys: exact zeros
+          kb16 = key < L ? kb16 : (unsigned short)0;
+          vb16 = key < L ? vb16 : (unsigned short)0;
+        }
         kp[(int64_t)key * a.dk_ss + d * 32 + l32] = kb16;
         vp[(int64_t)key * a.dv_ss + d * 32 + l32] = vb16;
         ck[d] += bf16_to_f32(kb16);
@@ -1218,7 +1423,13 @@ int g_attn_fwd_dma = 1;
 template <int D, bool CAUSAL>
 hipError_t launch_fwd(const MadnnAttnArgs& a, hipStream_t st) {
   const int nqb = (a.S + kRowsWG - 1) / kRowsWG;
-  if (a.drop_threshold != 0) {  // dropout: the register-staged kernel at every shape
+  if (a.seqlens != nullptr) {  // per-sequence lengths: the register-staged kernel at every shape, as dropout
+    if (a.drop_threshold != 0) {
+      hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, true, true>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, false, true>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
+    }
+  } else if (a.drop_threshold != 0) {  // dropout: the register-staged kernel at every shape
     hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, true>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
   } else if (D == 64 && g_attn_fwd_dma && a.S % kTile == 0) {
     hipLaunchKernelGGL((attn_fwd_dma_kernel<CAUSAL>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
@@ -1231,6 +1442,18 @@ hipError_t launch_fwd(const MadnnAttnArgs& a, hipStream_t st) {
 template <int D, bool CAUSAL>
 hipError_t launch_bwd(const MadnnAttnArgs& a, hipStream_t st) {
   const int nb = (a.S + kRowsWG - 1) / kRowsWG;
+  if (a.seqlens != nullptr) {  // per-sequence lengths: never the ring kernel
+    if (a.drop_threshold != 0) {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CAUSAL, true, true>), dim3(nb * a.B * a.H), dim3(kThreads), 0, st, a);
+      MADNN_HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, true, true>), dim3(nb * a.B * a.Hkv), dim3(kThreads), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CAUSAL, false, true>), dim3(nb * a.B * a.H), dim3(kThreads), 0, st, a);
+      MADNN_HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, false, true>), dim3(nb * a.B * a.Hkv), dim3(kThreads), 0, st, a);
+    }
+    return hipGetLastError();
+  }
   if (a.drop_threshold != 0) {
     hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CAUSAL, true>), dim3(nb * a.B * a.H), dim3(kThreads), 0, st, a);
     MADNN_HIP_CHECK(hipGetLastError());

@@ -1509,7 +1509,8 @@ void attn_check(const at::Tensor& t, const char* name, int64_t D) {
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "attention: ", name, " must be 16-byte aligned");
 }
 
-MadnnAttnArgs attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale) {
+MadnnAttnArgs attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                        const c10::optional<at::Tensor>& seqlens = c10::nullopt) {
   const int64_t D = q.size(3);
   TORCH_CHECK(madnn_attn_supported((int)D), "attention: head dim must be 64 or 128");
   attn_check(q, "q", D);
@@ -1531,6 +1532,14 @@ MadnnAttnArgs attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tens
   a.B = (int)q.size(0); a.S = (int)q.size(1); a.H = (int)q.size(2); a.Hkv = (int)k.size(2);
   a.scale = (float)scale;
   a.scale_log2 = (float)(scale * 1.4426950408889634);
+  // per-sequence lengths of a right-padded batch (null: dense).  The kernels clamp the values into
+  // [0, S] themselves: no host sync and no host-side value check.
+  if (seqlens.has_value() && seqlens->defined()) {
+    TORCH_CHECK(seqlens->scalar_type() == at::kInt && seqlens->dim() == 1 && seqlens->size(0) == q.size(0) &&
+                    seqlens->is_contiguous() && seqlens->device() == q.device(),
+                "attention: seqlens must be a contiguous int32 [B] tensor on the inputs' device");
+    a.seqlens = seqlens->data_ptr<int32_t>();
+  }
   return a;
 }
 
@@ -1551,8 +1560,9 @@ void attn_set_dropout(MadnnAttnArgs& a, double p, int64_t seed, int64_t offset) 
 }
 
 std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                                            bool causal, double scale, double p, int64_t seed, int64_t offset) {
-  MadnnAttnArgs a = attn_args(q, k, v, scale);
+                                            bool causal, double scale, double p, int64_t seed, int64_t offset,
+                                            const c10::optional<at::Tensor>& seqlens) {
+  MadnnAttnArgs a = attn_args(q, k, v, scale, seqlens);
   attn_set_dropout(a, p, seed, offset);
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor o = at::empty({q.size(0), q.size(1), q.size(2), q.size(3)}, q.options());
@@ -1568,8 +1578,8 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tenso
 void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
               const at::Tensor& o, const at::Tensor& lse, const at::Tensor& dq, const at::Tensor& dk,
               const at::Tensor& dv, bool causal, double scale, const c10::optional<at::Tensor>& colsum, double p,
-              int64_t seed, int64_t offset) {
-  MadnnAttnArgs a = attn_args(q, k, v, scale);
+              int64_t seed, int64_t offset, const c10::optional<at::Tensor>& seqlens) {
+  MadnnAttnArgs a = attn_args(q, k, v, scale, seqlens);
   attn_set_dropout(a, p, seed, offset);
   const int64_t D = q.size(3);
   TORCH_CHECK(o.is_contiguous() && o.sizes() == q.sizes(), "attn_bwd: o must be contiguous [B, S, H, D]");
@@ -1803,11 +1813,13 @@ TORCH_LIBRARY(madnn, m) {
       "bn_bwd_dual(Tensor dy, Tensor x, Tensor r, Tensor mask, Tensor? w, Tensor save_mean, Tensor save_invstd, "
       "Tensor? w_r, Tensor save_mean_r, Tensor save_invstd_r) -> Tensor[]");
   m.def(
-      "attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, float p=0.0, int seed=0, int offset=0) -> "
+      "attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, float p=0.0, int seed=0, int offset=0, "
+      "Tensor? seqlens=None) -> "
       "(Tensor, Tensor)");
   m.def(
       "attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, "
-      "Tensor(c!) dv, bool causal, float scale, Tensor(d!)? colsum=None, float p=0.0, int seed=0, int offset=0) -> ()");
+      "Tensor(c!) dv, bool causal, float scale, Tensor(d!)? colsum=None, float p=0.0, int seed=0, int offset=0, "
+      "Tensor? seqlens=None) -> ()");
   m.def("attn_dropout_mask(int B, int H, int S, float p, int seed, int offset) -> Tensor", &attn_dropout_mask);
   m.def("hidden_dropout_mask(int rows, int H, float p, int seed, int offset, int row0=0) -> Tensor",
         &hidden_dropout_mask);

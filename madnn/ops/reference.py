@@ -143,27 +143,63 @@ def cross_entropy(logits, targets, *, shift=False, vocab=None, ignore_index=-100
     return F.cross_entropy(logits[..., :v].reshape(-1, v).float(), targets.reshape(-1), ignore_index=ignore_index)
 
 
-def attention(q, k, v, *, causal=True, scale=None, dropout_p=0.0):
+def attention_valid(seqlens: torch.Tensor, S: int) -> torch.Tensor:
+    """bool [B, S]: position s of sequence b is a real token, ``s < clamp(seqlens[b], 0, S)``."""
+    return torch.arange(S, device=seqlens.device)[None, :] < seqlens.clamp(0, S)[:, None]
+
+
+def attention_seqlens_mask(seqlens: torch.Tensor, S: int, causal: bool) -> torch.Tensor:
+    """bool [B, 1, S, S] attention mask of a right-padded batch (True = attend): a valid query row sees
+    the valid keys (up to itself when causal).  A padded query row sees every key (up to itself when
+    causal) so that no row is empty -- an empty softmax row is NaN, which the later ``where`` would drop
+    in the forward but not in the backward; its output is replaced by zeros by the caller."""
+    valid = attention_valid(seqlens, S)
+    m = valid[:, None, None, :] | ~valid[:, None, :, None]
+    if causal:
+        m = m & torch.ones(S, S, dtype=torch.bool, device=seqlens.device).tril()
+    return m
+
+
+def attention(q, k, v, *, causal=True, scale=None, dropout_p=0.0, seqlens=None):
     """[B, S, H, D] / [B, S, Hkv, D] -> [B, S, H, D] via SDPA (fp32 oracle when given fp32).
     ``dropout_p`` is SDPA's own dropout (torch's mask, not K8's).  A ``scale`` that is not finite and
     positive is computed from plain ops in fp32 instead: SDPA's math path takes the square root of
-    the scale, and its fused bf16 backward on the device returned NaN gradients for a negative one."""
+    the scale, and its fused bf16 backward on the device returned NaN gradients for a negative one.
+
+    ``seqlens`` (integer [B]): a right-padded batch, K8's contract (:func:`madnn.ops.attention`).
+    Padded positions of q, k and v are replaced by zeros with ``torch.where`` before anything is
+    computed (their values, NaN included, reach no result and their gradients are exact zeros), valid
+    query rows see the valid keys only, and padded rows of the output are exact zeros."""
     import torch.nn.functional as F
 
     h, hkv = q.size(2), k.size(2)
+    mask = None
+    if seqlens is not None:
+        S = q.size(1)
+        seqlens = seqlens.to(q.device)
+        valid = attention_valid(seqlens, S)[:, :, None, None]
+        q, k, v = (torch.where(valid, t, torch.zeros((), dtype=t.dtype, device=t.device)) for t in (q, k, v))
+        mask = attention_seqlens_mask(seqlens, S, causal)
     if scale is not None and not (math.isfinite(scale) and scale > 0):
         qt, kt, vt = (t.transpose(1, 2).float() for t in (q, k, v))
         if h != hkv:
             kt, vt = kt.repeat_interleave(h // hkv, dim=1), vt.repeat_interleave(h // hkv, dim=1)
         s = (qt @ kt.transpose(-1, -2)) * scale
-        if causal:
+        if mask is not None:
+            s = s.masked_fill(~mask, float("-inf"))
+        elif causal:
             n = s.size(-1)
             s = s.masked_fill(~torch.ones(n, n, dtype=torch.bool, device=s.device).tril(), float("-inf"))
         p = F.dropout(torch.softmax(s, dim=-1), dropout_p)
-        return (p @ vt).to(q.dtype).transpose(1, 2).contiguous()
-    o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), dropout_p=dropout_p,
-                                       is_causal=causal, scale=scale, enable_gqa=h != hkv)
-    return o.transpose(1, 2).contiguous()
+        o = (p @ vt).to(q.dtype).transpose(1, 2).contiguous()
+    else:
+        o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), attn_mask=mask,
+                                           dropout_p=dropout_p, is_causal=causal and mask is None, scale=scale,
+                                           enable_gqa=h != hkv)
+        o = o.transpose(1, 2).contiguous()
+    if seqlens is not None:
+        o = torch.where(valid, o, torch.zeros((), dtype=o.dtype, device=o.device))
+    return o
 
 
 DROPOUT_BITS = 8  # K8's dropout mask: one byte per attention probability
