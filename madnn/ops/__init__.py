@@ -377,6 +377,12 @@ def _attached(t: Optional[torch.Tensor], name: str, strict: bool = False):
 
 
 # ---------------------------------------------------------------------- K5
+def _same_layout(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Equal shapes, and equal strides wherever the size is not 1 (a size-1 dimension's stride is arbitrary: a
+    view of a batch-1 NHWC tensor reports another one than the tensor it views)."""
+    return a.shape == b.shape and all(sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()) if n != 1)
+
+
 class _BNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, running_mean, running_var, nbt, training, momentum, eps, relu, stats):
@@ -400,7 +406,7 @@ class _BNFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, mask, weight, mean, invstd, scale, shift = ctx.saved_tensors
         need_w = ctx.has_w and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        defer = ctx.defer and dy.dtype == x.dtype and dy.stride() == x.stride()
+        defer = ctx.defer and dy.dtype == x.dtype and _same_layout(dy, x)
         dx, dw, db, dres = torch.ops.madnn.bn_bwd(dy, x, mask if mask.numel() else None, ctx.has_res, weight,
                                                   mean, invstd, scale, shift, ctx.relu, need_w, not defer)
         if defer:
@@ -477,7 +483,7 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, num_batches_track
                                               or (residual is not None and residual.requires_grad))
     fused = bn_supported(x, weight) and (training or not needs_grad) and momentum is not None
     if fused and residual is not None:
-        fused = residual.dtype == x.dtype and residual.shape == x.shape and residual.stride() == x.stride()
+        fused = residual.dtype == x.dtype and _same_layout(residual, x)
     if fused:
         _need_native("batch_norm_act")
         return _BNFn.apply(x, weight, bias, residual, running_mean, running_var,
@@ -512,7 +518,7 @@ def batch_norm_dual_supported(x: torch.Tensor, r: torch.Tensor, bn, bn_r) -> boo
     """Shapes/modes :func:`batch_norm_add_bn_relu` runs as one fused kernel pair."""
     return (isinstance(x, torch.Tensor) and isinstance(r, torch.Tensor)   # not e.g. fx tracing proxies
             and x.dtype == torch.bfloat16 and bn_supported(x, bn.weight) and r.shape == x.shape
-            and r.dtype == x.dtype and r.stride() == x.stride() and _bn_trainable(bn) and _bn_trainable(bn_r))
+            and r.dtype == x.dtype and _same_layout(r, x) and _bn_trainable(bn) and _bn_trainable(bn_r))
 
 
 def batch_norm_add_bn_relu(x, r, bn, bn_r, stats=None, stats_r=None):

@@ -406,9 +406,18 @@ int64_t* nbt_ptr(const c10::optional<at::Tensor>& t, const char* op) {
   return t->data_ptr<int64_t>();
 }
 
-// dy in x's strides and dtype (a copy only if it is not already)
+// Equal sizes, and equal strides wherever the size is not 1: the same memory layout.  (The stride of a size-1
+// dimension is arbitrary -- a view of a batch-1 NHWC tensor reports another one than the tensor it views.)
+bool same_layout(const at::Tensor& a, const at::Tensor& b) {
+  if (a.sizes() != b.sizes()) return false;
+  for (int64_t d = 0; d < a.dim(); ++d)
+    if (a.size(d) != 1 && a.stride(d) != b.stride(d)) return false;
+  return true;
+}
+
+// dy in x's layout and dtype (a copy only if it is not already)
 at::Tensor dy_like(const at::Tensor& dy, const at::Tensor& x) {
-  if (dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type()) return dy;
+  if (same_layout(dy, x) && dy.scalar_type() == x.scalar_type()) return dy;
   return at::empty_like(x).copy_(dy);
 }
 
@@ -439,7 +448,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
   const int64_t M = bn_rows(x, C);
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   at::Tensor y = at::empty_like(x);
-  if (res.has_value()) TORCH_CHECK(res->sizes() == x.sizes() && res->strides() == x.strides(), "bn residual layout");
+  if (res.has_value()) TORCH_CHECK(same_layout(*res, x), "bn residual layout");
   if (!training) TORCH_CHECK(run_mean.has_value() && run_var.has_value(), "bn eval needs running stats");
   auto fo = x.options().dtype(at::kFloat);
   at::Tensor save_mean = at::empty({C}, fo), save_invstd = at::empty({C}, fo);
@@ -510,7 +519,7 @@ std::vector<at::Tensor> bn_fwd_dual(const at::Tensor& x, const at::Tensor& r, co
   const int64_t C = x.size(1);
   TORCH_CHECK(madnn_bn_supported((int)C), "bn kernel needs C % 8 == 0 and C <= 2048, got ", C);
   const int64_t M = bn_rows(x, C);
-  TORCH_CHECK(r.sizes() == x.sizes() && r.strides() == x.strides(), "bn_fwd_dual: residual layout");
+  TORCH_CHECK(same_layout(r, x), "bn_fwd_dual: residual layout");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto fo = x.options().dtype(at::kFloat);
   std::vector<at::Tensor> out;
@@ -545,8 +554,7 @@ std::vector<at::Tensor> bn_bwd_dual(const at::Tensor& dy, const at::Tensor& x, c
   check_dev(x, "x");
   const int64_t C = x.size(1);
   const int64_t M = bn_rows(x, C);
-  TORCH_CHECK(r.sizes() == x.sizes() && r.strides() == x.strides() && r.scalar_type() == x.scalar_type(),
-              "bn_bwd_dual: residual layout");
+  TORCH_CHECK(same_layout(r, x) && r.scalar_type() == x.scalar_type(), "bn_bwd_dual: residual layout");
   const uint8_t* mk = mask_ptr(mask, x.numel(), "bn_bwd_dual");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   at::Tensor dyc = dy_like(dy, x);
@@ -576,10 +584,8 @@ std::vector<at::Tensor> bn_bwd_dual_coef(const at::Tensor& dy, const at::Tensor&
   const int64_t C = x.size(1);
   const int64_t M = bn_rows(x, C);
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "bn_bwd_dual_coef: bf16 only");
-  TORCH_CHECK(r.sizes() == x.sizes() && r.strides() == x.strides() && r.scalar_type() == x.scalar_type(),
-              "bn_bwd_dual_coef: residual layout");
-  TORCH_CHECK(dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type(),
-              "bn_bwd_dual_coef: dy / x of one layout");
+  TORCH_CHECK(same_layout(r, x) && r.scalar_type() == x.scalar_type(), "bn_bwd_dual_coef: residual layout");
+  TORCH_CHECK(same_layout(dy, x) && dy.scalar_type() == x.scalar_type(), "bn_bwd_dual_coef: dy / x of one layout");
   const uint8_t* mk = mask_ptr(mask, x.numel(), "bn_bwd_dual_coef");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto fo = x.options().dtype(at::kFloat);
@@ -736,7 +742,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_bwd_coef(const at::Tensor& dy,
   check_dev(x, "x");
   const int64_t C = x.size(1);
   const int64_t M = bn_rows(x, C);
-  TORCH_CHECK(dy.strides() == x.strides() && dy.scalar_type() == x.scalar_type(), "bn_bwd_coef: dy / x of one layout");
+  TORCH_CHECK(same_layout(dy, x) && dy.scalar_type() == x.scalar_type(), "bn_bwd_coef: dy / x of one layout");
   const uint8_t* mk = mask_ptr(mask, x.numel(), "bn_bwd_coef");
   at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto fo = x.options().dtype(at::kFloat);
@@ -1058,7 +1064,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_bwd_ext(const at::Tensor& dy, 
   check_dev(x, "x");
   const int64_t C = x.size(1);
   const int64_t M = bn_rows(x, C);
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && dy.scalar_type() == at::kBFloat16 && dy.strides() == x.strides(),
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && dy.scalar_type() == at::kBFloat16 && same_layout(dy, x),
               "bn_bwd_ext: bf16 dy / x of one layout");
   TORCH_CHECK(partial.scalar_type() == at::kFloat && partial.is_contiguous() && partial.dim() == 3 &&
                   partial.size(1) == 2 && partial.size(2) == C,
