@@ -89,13 +89,13 @@ def main():
 
 def ab_native(a):
     """K8 forward / backward times with a native tunable ON vs OFF, interleaved rounds in one process."""
-    import ctypes
+    import functools
 
     from madnn import ops
 
     assert ops.load_kernels()
     fn, key, von, voff = a.native.split(":")
-    knob = getattr(ctypes.CDLL(str(ops.kernels_path())), fn)
+    knob = functools.partial(ops.native_tune, fn.removeprefix("madnn_").removesuffix("_tune"))
     dev = torch.device("cuda")
     rows = []
     for name, B, S, H, HKV, D, causal in SHAPES:

@@ -9,7 +9,7 @@ Prints one JSON line per (shape, arm) with forward and backward times and TFLOP/
 from __future__ import annotations
 
 import argparse
-import ctypes
+import functools
 import json
 import os
 import statistics
@@ -41,7 +41,7 @@ def main():
     from madnn import ops
 
     assert ops.load_kernels()
-    tune = ctypes.CDLL(str(ops.kernels_path())).madnn_attn_tune
+    tune = functools.partial(ops.native_tune, "attn")
     key, off, on = (int(v) for v in a.knob.split(":"))
     rows = []
     for name, S, H, HKV, D, causal, B in [("gpt2-medium", 1024, 16, 16, 64, True, a.batch),

@@ -25,7 +25,7 @@ over the rounds) of (a), the ratio (b) / (a) and whether (c) - (b) exceeds that 
 from __future__ import annotations
 
 import argparse
-import ctypes
+import functools
 import json
 import os
 import statistics
@@ -76,7 +76,7 @@ def child(name: str, batch: int, rounds: int, iters: int) -> dict:
                                            enable_gqa=H != HKV)
         return o.transpose(1, 2).contiguous()
 
-    tune = ctypes.CDLL(str(ops.kernels_path())).madnn_attn_tune
+    tune = functools.partial(ops.native_tune, "attn")
 
     arms = {"dense": dense, "varlen": varlen, "sdpa": sdpa, "staged": dense}
 

@@ -14,7 +14,7 @@ interleaved windows, medians; first the off arm against itself for the spread (`
     python bench/conv1x1_ring_ab.py step --batch 2048 --windows 6 --out k9_ring_step.json
 """
 import argparse
-import ctypes
+import functools
 import json
 import os
 import statistics
@@ -52,7 +52,7 @@ def kernel_ab(args):
 
     assert ops.load_kernels()
     m = torch.ops.madnn
-    tune = ctypes.CDLL(str(ops.kernels_path())).madnn_conv1x1_tune
+    tune = functools.partial(ops.native_tune, "conv1x1")
     start = tune(3, -1)
     arms = {"staged": 0, "ring": 1} if start >= 0 else {"staged": None}
     dev = torch.device("cuda", 0)

@@ -2,11 +2,11 @@
 """K3 LayerNorm forward / backward at the GPT-2 medium (131072 x 1024) and BERT-large (65536 x 1024)
 shapes, bf16, against the launch-grid knobs (madnn_norm_tune 0 / 1): time and achieved bandwidth
 (forward 4 B, backward 6 B per element).  python bench/norm_probe.py"""
-import ctypes, statistics, torch, sys, os, json
+import functools, statistics, torch, sys, os, json
 sys.path.insert(0, os.getcwd())
 from madnn import ops
 assert ops.load_kernels()
-tune = ctypes.CDLL(str(ops.kernels_path())).madnn_norm_tune
+tune = functools.partial(ops.native_tune, "norm")
 def timeit(fn, iters=20):
     for _ in range(3): fn()
     ts=[]

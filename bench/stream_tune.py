@@ -5,7 +5,6 @@ launch knobs timed in interleaved rounds (rotated order, medians), with the anal
     python bench/stream_tune.py --out gpurun_out/stream_tune.json
 """
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -27,12 +26,12 @@ def _time(fn, iters=10):
     return s.elapsed_time(e) / iters * 1e3   # us
 
 
-def sweep(name, lib, setter, settings, fn, nbytes, rounds):
+def sweep(name, tune, setter, settings, fn, nbytes, rounds):
     times = {repr(st): [] for st in settings}
     for r in range(rounds):
         order = settings[r % len(settings):] + settings[:r % len(settings)]
         for st in order:
-            setter(lib, st)
+            setter(tune, st)
             times[repr(st)].append(_time(fn))
     out = []
     for st in settings:
@@ -51,22 +50,22 @@ def main():
     from madnn import ops
 
     assert torch.cuda.is_available() and ops.load_kernels()
-    lib = ctypes.CDLL(str(ops.kernels_path()))
+    tune = ops.native_tune
     res = []
     x = torch.randn(a.rows, 4096, device="cuda", dtype=torch.bfloat16)
 
-    def set_gelu(lib, st):
-        lib.madnn_gelu_tune(0, st[0])
-        lib.madnn_gelu_tune(1, st[1])
+    def set_gelu(tune, st):
+        tune("gelu", 0, st[0])
+        tune("gelu", 1, st[1])
 
-    res += sweep("gelu_fwd [M, 4096]", lib, set_gelu, [(1, 8), (8, 4), (1, 4), (2, 8)],
+    res += sweep("gelu_fwd [M, 4096]", tune, set_gelu, [(1, 8), (8, 4), (1, 4), (2, 8)],
                  lambda: ops.gelu_tanh(x), 2 * x.numel() * 2, a.rounds)
-    set_gelu(lib, (1, 8))
+    set_gelu(tune, (1, 8))
     # the fused GELU backward + bias-gradient pass (K11): workgroups per CU
     dy = torch.randn_like(x)
-    res += sweep("bias_grad+gelu_bwd [M, 4096]", lib, lambda l, st: l.madnn_bias_tune(1, st), [4, 2, 1, 8],
+    res += sweep("bias_grad+gelu_bwd [M, 4096]", tune, lambda t, st: t("bias", 1, st), [4, 2, 1, 8],
                  lambda: ops.bias_grad(dy, x, torch.bfloat16), 3 * x.numel() * 2, a.rounds)
-    lib.madnn_bias_tune(1, 4)
+    tune("bias", 1, 4)
     del x, dy
     # FusedAdam over 64M parameters (fp32 master / m / v, bf16 grad and model copy)
     from madnn.optim import FusedAdam
@@ -75,21 +74,21 @@ def main():
     p.grad = torch.randn_like(p)
     opt = FusedAdam([p], lr=1e-4)
     opt.step()
-    res += sweep("adam [64M]", lib, lambda l, st: l.madnn_optim_tune(0, st), [4, 2, 1, 8], opt.step,
+    res += sweep("adam [64M]", tune, lambda t, st: t("optim", 0, st), [4, 2, 1, 8], opt.step,
                  p.numel() * (4 * 3 * 2 + 2 + 2), a.rounds)
-    lib.madnn_optim_tune(0, 4)
+    tune("optim", 0, 4)
     del p, opt
     h = torch.randn(a.rows, 1024, device="cuda", dtype=torch.bfloat16)
     w = torch.ones(1024, device="cuda", dtype=torch.bfloat16)
     b = torch.zeros(1024, device="cuda", dtype=torch.bfloat16)
 
-    def set_norm(lib, st):
-        lib.madnn_norm_tune(0, st)
+    def set_norm(tune, st):
+        tune("norm", 0, st)
 
     with torch.no_grad():
-        res += sweep("norm_fwd [M, 1024]", lib, set_norm, [8, 16, 32], lambda: ops.layer_norm(h, w, b),
+        res += sweep("norm_fwd [M, 1024]", tune, set_norm, [8, 16, 32], lambda: ops.layer_norm(h, w, b),
                      2 * h.numel() * 2, a.rounds)
-    set_norm(lib, 8)
+    set_norm(tune, 8)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)

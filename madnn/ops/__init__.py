@@ -97,6 +97,30 @@ def _need_native(what: str):
     return torch.ops.madnn
 
 
+_ctypes_lib = []  # the kernel library's ctypes handle, opened once
+_tune_fns = {}    # knob family -> its prepared madnn_<family>_tune
+
+
+def native_tune(family: str, key: int, value: int = -1) -> int:
+    """The native A/B knob ``madnn_<family>_tune(key, value)`` of the kernel library (declared in csrc/abi.h;
+    the keys are documented there or at the knob's definition).  Returns what the C function returns: as a
+    rule the previous value, with a negative ``value`` only reading.  ``ValueError`` for an unknown family."""
+    fn = _tune_fns.get(family)
+    if fn is None:
+        _need_native(f"native_tune({family!r})")
+        import ctypes
+
+        if not _ctypes_lib:
+            _ctypes_lib.append(ctypes.CDLL(str(_KERNELS)))
+        try:
+            fn = getattr(_ctypes_lib[0], f"madnn_{family}_tune")
+        except AttributeError:
+            raise ValueError(f"madnn: no native tune knob family {family!r} (madnn_{family}_tune)") from None
+        fn.argtypes, fn.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_int
+        _tune_fns[family] = fn
+    return int(fn(int(key), int(value)))
+
+
 def _is_dev(t: torch.Tensor) -> bool:
     return t.device.type == "cuda"
 
@@ -938,19 +962,13 @@ K9_RING = os.environ.get("MADNN_K9_RING", "1") != "0"
 # A/B switch: the deep 1x1 forwards (Cin >= 256, Cout >= Cin, 256-multiples of pixels and Cout) and the deep plain
 # data grad run on K12P, the forwards with the BatchNorm statistics in its epilogue (conv.hip use_deep).  Off: K9.
 K9_DEEP = os.environ.get("MADNN_K9_DEEP", "1") != "0"
-_K9_TUNE = []
 
 
 def conv1x1_tune(key: int, value: int = -1) -> int:
     """K9's native tunables (``madnn_conv1x1_tune``): key 0 the forward / data-grad persistent grid target,
     1 the weight-grad workgroups, 2 the XCD remap, 3 the ring switch, 4 the deep-shapes-on-K12P switch.  Sets
     ``value`` (>= 0) and returns the previous one; ``value < 0`` only reads."""
-    _need_native("conv1x1_tune")
-    if not _K9_TUNE:
-        import ctypes
-
-        _K9_TUNE.append(ctypes.CDLL(str(_KERNELS)).madnn_conv1x1_tune)
-    return int(_K9_TUNE[0](int(key), int(value)))
+    return native_tune("conv1x1", key, value)
 
 
 def _k9():
@@ -2267,7 +2285,7 @@ __all__ = [
     "max_pool2d", "max_pool_supported", "conv1x1", "conv1x1_route", "batch_norm_add_bn_relu",
     "batch_norm_dual_supported", "bn_relu_conv1x1", "bn_relu_maxpool",
     "bn_relu_maxpool_supported", "bn_relu_conv3x3", "bn_relu_conv3x3_supported",
-    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "conv1x1_tune", "stem_conv", "stem_supported", "stem_bn_relu_maxpool", "stem_bn_relu_maxpool_supported", "native_available", "load_kernels", "kernels_path", "hidden_supported", "reference",
+    "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "conv1x1_tune", "stem_conv", "stem_supported", "stem_bn_relu_maxpool", "stem_bn_relu_maxpool_supported", "native_available", "native_tune", "load_kernels", "kernels_path", "hidden_supported", "reference",
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
 ]

@@ -69,6 +69,7 @@
 //  * the dropout mask stays the same function of the absolute (b, h, q, k).
 #include <type_traits>
 
+#include "abi.h"
 #include "attn.h"
 #include "dropout.h"
 #include "mfma.h"
@@ -1417,8 +1418,8 @@ __global__ __launch_bounds__(256) void attn_dropout_mask_kernel(uint8_t* __restr
 // madnn_attn_tune keys (A/B and the tests of the register-staged fallbacks, which serve sequence
 // lengths that are not multiples of 64 and D = 128): 7 = D = 64 dK/dV on the 3-stage LDS-DMA ring,
 // 8 = D = 64 forward on the K / V LDS-DMA ring (0: the register-staged kernels)
-int g_attn_dkdv_dma = 1;
-int g_attn_fwd_dma = 1;
+static int g_attn_dkdv_dma = 1;
+static int g_attn_fwd_dma = 1;
 
 template <int D, bool CAUSAL>
 hipError_t launch_fwd(const MadnnAttnArgs& a, hipStream_t st) {
@@ -1495,7 +1496,6 @@ hipError_t madnn_attn_fwd(const MadnnAttnArgs* a, int D, int causal, hipStream_t
   return hipErrorInvalidValue;
 }
 
-// rows of MadnnAttnArgs::cpart: one per (batch, 128-row sequence block)
 int64_t madnn_attn_colsum_rows(int B, int S) { return (int64_t)B * ((S + kRowsWG - 1) / kRowsWG); }
 
 hipError_t madnn_attn_colsum_finalize(const float* cpart, int64_t R, int64_t C, void* out, int out_bf16,
@@ -1506,8 +1506,6 @@ hipError_t madnn_attn_colsum_finalize(const float* cpart, int64_t R, int64_t C, 
   return hipGetLastError();
 }
 
-// threshold = floor((1 - p) * 256 + 0.5): 1..256 for a usable p, 0 when p quantises to keep-nothing,
-// -1 for p outside [0, 1)
 int madnn_attn_dropout_threshold(double p) {
   if (!(p >= 0.0 && p < 1.0)) return -1;
   return (int)((1.0 - p) * 256.0 + 0.5);

@@ -13,6 +13,7 @@
 // row slots and walks rows with 4 in flight per lane; its row slots are summed in LDS into ONE
 // fp32 partial row.  A finalize (32 columns x 32 row slices per 1024-lane block) sums the
 // partial rows in a fixed order (deterministic, no float atomics) and casts to the bias dtype.
+#include "abi.h"
 #include "common.h"
 #include "gelu.h"
 
@@ -170,7 +171,6 @@ int madnn_bias_tune(int gelu, int wg_per_cu) {
 
 int madnn_bias_grad_supported(int64_t M, int N) { return N % 8 == 0 && N > 0 && M > 0; }
 
-// partial rows R: ~wg_per_cu workgroups per CU in total, each walking >= 4 row steps
 int madnn_bias_grad_rows(int64_t M, int N, int gelu) {
   const BiasGeom g = bias_geom(N);
   int64_t r = (g_bias_wg_per_cu[gelu ? 1 : 0] * kNumCU + g.strips - 1) / g.strips;
@@ -196,7 +196,6 @@ int madnn_gelu_tune(int key, int value) {
   return old;
 }
 
-// kind: kGeluTanh (1) or kGeluErf (2)
 hipError_t madnn_gelu_fwd(const void* x, void* y, int64_t n, int dt, int kind, hipStream_t stream) {
   if (kind != kGeluTanh && kind != kGeluErf) return hipErrorInvalidValue;
   if (n % 8) return hipErrorInvalidValue;
@@ -225,8 +224,6 @@ hipError_t madnn_gelu_fwd(const void* x, void* y, int64_t n, int dt, int kind, h
   return hipGetLastError();
 }
 
-// dy, pre, dp: [M, N] of dtype xdt; partial: [R, N] fp32 with R = madnn_bias_grad_rows(M, N, pre != 0);
-// db: [N] of odt; kind: the GELU whose backward runs on pre (kGeluTanh / kGeluErf)
 hipError_t madnn_bias_grad(const void* dy, const void* pre, void* dp, int64_t M, int N, int xdt, float* partial,
                            void* db, int odt, int kind, hipStream_t stream) {
   if (!madnn_bias_grad_supported(M, N)) return hipErrorInvalidValue;

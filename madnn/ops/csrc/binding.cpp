@@ -1,6 +1,6 @@
 // torch.ops.madnn.* registration for the hand-written gfx950 kernels.
 //
-// The kernels live in bucket.hip / optim.hip / norm.hip behind a C ABI; this
+// The kernels live in the .hip files behind the C ABI that abi.h declares; this
 // file only validates tensors, fetches the current HIP stream and launches.
 // Registered for the CUDA dispatch key, which is what ROCm PyTorch uses for
 // HIP device tensors.  CPU tensors never reach this file: the Python layer
@@ -14,147 +14,7 @@
 #include <cmath>
 #include <vector>
 
-#include "attn.h"
-
-extern "C" {
-hipError_t madnn_bucket_pack(void* const*, const int64_t*, const int64_t*, int, void*, int, int, float, hipStream_t);
-hipError_t madnn_bucket_unpack(void* const*, const int64_t*, const int64_t*, int, void*, int, int, float, hipStream_t);
-hipError_t madnn_flat_scale_cast(const void*, void*, int64_t, int, int, float, hipStream_t);
-hipError_t madnn_sgd_step(float*, const void*, int, float*, void*, int, int64_t, float, float, float, float, int, int,
-                          float, const float*, hipStream_t);
-hipError_t madnn_adam_step(float*, const void*, int, float*, float*, void*, int, int64_t, float, float, float, float,
-                           float, int, float, float, float, const float*, hipStream_t);
-int madnn_sqnorm_grid(int64_t);
-hipError_t madnn_sqnorm_partial(const void*, int, int64_t, float, float*, int, hipStream_t);
-hipError_t madnn_norm_finalize(const float*, int, float, float*, hipStream_t);
-hipError_t madnn_norm_fwd(const void*, const void*, const void*, const void*, void*, void*, float*, float*, int64_t,
-                          int, float, int, int, int, hipStream_t);
-int64_t madnn_norm_bwd_workspace(int64_t, int);
-hipError_t madnn_norm_bwd(const void*, const void*, const void*, const float*, const float*, const void*, void*, void*,
-                          void*, void*, int, float*, int64_t, int, int, int, int, hipStream_t);
-int madnn_bn_supported(int);
-int madnn_bn_partial_rows(int64_t, int);
-hipError_t madnn_bn_fwd(const void*, const void*, void*, unsigned char*, int64_t, int, int, int, int, float, float,
-                        const float*, const float*, float*, float*, int64_t*, float*, float*, float*, float*, float*,
-                        const float*, int, hipStream_t);
-int madnn_bias_grad_supported(int64_t, int);
-int madnn_bias_grad_rows(int64_t, int, int);
-hipError_t madnn_bias_grad(const void*, const void*, void*, int64_t, int, int, float*, void*, int, int, hipStream_t);
-hipError_t madnn_gelu_fwd(const void*, void*, int64_t, int, int, hipStream_t);
-hipError_t madnn_rope_qkv(const void*, void*, const float*, const float*, int64_t, int, int, int, int, int, hipStream_t);
-hipError_t madnn_swiglu_fwd(const void*, void*, int64_t, int, hipStream_t);
-hipError_t madnn_swiglu_bwd(const void*, const void*, void*, int64_t, int, hipStream_t);
-int madnn_attn_supported(int);
-hipError_t madnn_attn_fwd(const MadnnAttnArgs*, int, int, hipStream_t);
-hipError_t madnn_attn_bwd(const MadnnAttnArgs*, int, int, hipStream_t);
-int64_t madnn_attn_colsum_rows(int, int);
-hipError_t madnn_attn_colsum_finalize(const float*, int64_t, int64_t, void*, int, hipStream_t);
-int madnn_attn_dropout_threshold(double);
-hipError_t madnn_attn_dropout_mask(uint8_t*, int, int, int, uint32_t, uint64_t, uint64_t, hipStream_t);
-hipError_t madnn_norm_drop_fwd(const void*, const void*, const void*, const void*, void*, void*, float*, float*, int64_t,
-                               int, float, int, int, int, uint32_t, uint64_t, uint64_t, hipStream_t);
-hipError_t madnn_norm_drop_bwd(const void*, const void*, const void*, const float*, const float*, const void*, void*,
-                               void*, void*, void*, void*, int, float*, int64_t, int, int, int, int, uint32_t, uint64_t,
-                               uint64_t, hipStream_t);
-hipError_t madnn_dropout_add(const void*, const void*, void*, int64_t, int, int, uint32_t, uint64_t, uint64_t, hipStream_t);
-hipError_t madnn_hidden_dropout_mask(uint8_t*, int64_t, int, int64_t, uint32_t, uint64_t, uint64_t, hipStream_t);
-int madnn_maxpool_supported(int64_t, int, int);
-hipError_t madnn_maxpool_fwd(const void*, void*, void*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-int madnn_pool_bn_supported(int64_t, int);
-int madnn_pool_bn_bwd_rows(int64_t, int);
-int madnn_pool_bn_bwd_pooled_rows(int64_t, int);
-hipError_t madnn_pool_bn_fwd(const void*, const float*, const float*, void*, void*, void*, int, int, int, int, int, int,
-                             int, hipStream_t);
-hipError_t madnn_pool_bn_bwd_pooled(const void*, const void*, const float*, const float*, const float*, const float*,
-                                    const float*, float*, float*, float*, float*, int64_t, int64_t, int, hipStream_t);
-hipError_t madnn_pool_bn_bwd(const void*, const void*, const void*, const float*, const float*, const float*,
-                             const float*, const float*, void*, float*, float*, float*, float*, int, int, int, int, int,
-                             int, int, hipStream_t);
-hipError_t madnn_maxpool_bwd(const void*, const void*, void*, int, int, int, int, int, int, int, int, int, int,
-                             hipStream_t);
-hipError_t madnn_xent_fwd(const void*, int, const int64_t*, int64_t, int64_t, int64_t, int, int, float*, float*,
-                          hipStream_t);
-hipError_t madnn_xent_bwd(const void*, int, const int64_t*, const float*, int64_t, int64_t, int64_t, int, int, int64_t,
-                          const float*, void*, hipStream_t);
-int madnn_xent_fused_chunks(int64_t);
-hipError_t madnn_xent_fused(const void*, int, const int64_t*, int64_t, int64_t, int64_t, int, int, int64_t,
-                            const float*, float*, void*, hipStream_t);
-hipError_t madnn_xent_rescale(void*, int, int64_t, const float*, hipStream_t);
-hipError_t madnn_bn_bwd(const void*, const void*, const unsigned char*, int, void*, void*, int64_t, int, int, int,
-                        const float*, const float*, const float*, const float*, const float*, float*, float*, float*,
-                        float*, hipStream_t);
-hipError_t madnn_bn_fwd_dual(const void*, const void*, void*, unsigned char*, int64_t, int, float, float, const float*,
-                             const float*, float*, float*, int64_t*, float*, float*, float*, float*, const float*, int,
-                             float, float, const float*, const float*, float*, float*, int64_t*, float*, float*,
-                             float*, float*, const float*, int, float*, hipStream_t);
-hipError_t madnn_bn_bwd_dual(const void*, const void*, const void*, const unsigned char*, void*, void*, int64_t, int,
-                             const float*, const float*, const float*, const float*, const float*, const float*,
-                             float*, float*, float*, float*, float*, float*, hipStream_t);
-hipError_t madnn_bn_bwd_dual_coef(const void*, const void*, const void*, const unsigned char*, int64_t, int,
-                                  const float*, const float*, const float*, const float*, const float*, const float*,
-                                  float*, float*, float*, float*, float*, float*, hipStream_t);
-hipError_t madnn_bn_bwd_coef(const void*, const void*, const unsigned char*, int, int64_t, int, int, int, const float*,
-                             const float*, const float*, const float*, const float*, float*, float*, float*, float*,
-                             hipStream_t);
-int madnn_bn3_conv3_bwd_supported(int64_t, int64_t);
-int madnn_bn3_conv3_bwd_groups(int64_t);
-hipError_t madnn_bn3_conv3_bwd(const void*, const void*, const unsigned char*, const float*, const void*, const void*,
-                               const void*, const float*, const float*, void*, float*, float*, void*, int, int64_t,
-                               int64_t, int64_t, hipStream_t);
-int madnn_conv1x1_supported(int64_t, int64_t);
-int madnn_conv1x1_stat_rows(int64_t, int64_t, int64_t);
-hipError_t madnn_conv1x1_fwd(const void*, const void*, void*, float*, int64_t, int64_t, int64_t, hipStream_t);
-hipError_t madnn_conv1x1_dgrad(const void*, const void*, void*, const void*, int64_t, int64_t, int64_t, const void*,
-                               const float*, const float*, float*, hipStream_t, const unsigned char* = nullptr);
-int madnn_conv1x1_dgrad_rows(int64_t, int64_t, int64_t);
-int64_t madnn_conv1x1_wgrad_ws(int64_t, int64_t, int64_t);
-hipError_t madnn_conv1x1_wgrad(const void*, const void*, void*, int, float*, int64_t, int64_t, int64_t, hipStream_t);
-hipError_t madnn_bn_coef(const void*, int64_t, int, float, float, const float*, const float*, float*, float*, int64_t*,
-                         float*, float*, float*, float*, float*, const float*, int, hipStream_t);
-int madnn_stem_supported(int, int);
-int madnn_stem_stat_rows(int, int, int);
-hipError_t madnn_stem_fwd(const void*, const void*, void*, float*, int, int, int, hipStream_t);
-int64_t madnn_stem_wgrad_ws(int, int, int);
-hipError_t madnn_stem_wgrad(const void*, const void*, float*, float*, int, int, int, hipStream_t);
-hipError_t madnn_stem_wgrad_bnp(const void*, const void*, const void*, const void*, const float*, const float*,
-                                const float*, const float*, const float*, float*, float*, int, int, int, int,
-                                hipStream_t);
-int madnn_gemm_supported(int64_t, int64_t, int64_t, int64_t, int64_t);
-int madnn_conv3x3_supported(int, int, int, int);
-int madnn_conv3x3_stat_rows(int64_t);
-hipError_t madnn_conv3x3_fwd(const void*, const void*, void*, float*, int, int, int, int, int, hipStream_t);
-int madnn_conv3x3_s2_supported(int, int, int, int);
-int madnn_conv3x3_s2_stat_rows(int, int, int);
-hipError_t madnn_conv3x3_fwd_s2(const void*, const void*, void*, float*, int, int, int, int, int, hipStream_t);
-int64_t madnn_conv3x3_wgrad_ws(int, int, int, int, int);
-hipError_t madnn_conv3x3_fwd_bnb(const void*, const void*, void*, float*, const void*, const float*, const float*, int,
-                                 int, int, int, int, hipStream_t);
-hipError_t madnn_bn_bwd_ext(const void*, const void*, void*, int64_t, int, int, const float*, const float*,
-                            const float*, const float*, const float*, float*, float*, float*, const float*, int, float*,
-                            hipStream_t);
-int madnn_bn_prereduce_floats(int);
-hipError_t madnn_conv3x3_wgrad(const void*, const void*, float*, void*, int, int, int, int, int, int, hipStream_t);
-hipError_t madnn_linear_fwd(const void*, const void*, const void*, int, const void*, void*, void*, int, int64_t,
-                            int64_t, int64_t, hipStream_t);
-hipError_t madnn_linear_dgrad(const void*, const void*, const void*, void*, int64_t, int64_t, int64_t, hipStream_t);
-int madnn_wgrad_splits(int64_t, int64_t, int64_t);
-hipError_t madnn_linear_wgrad4h(const void*, const void*, void*, float*, int, int, int64_t, int64_t, int64_t,
-                                hipStream_t);
-hipError_t madnn_linear_wgrad4(const void*, const void*, void*, float*, int, int, int64_t, int64_t, int64_t,
-                               hipStream_t);
-hipError_t madnn_linear_wgrad(const void*, const void*, void*, float*, int, int, int64_t, int64_t, int64_t,
-                              hipStream_t);
-int madnn_gemmp_supported(int64_t, int64_t, int64_t, int);
-hipError_t madnn_linear_fwd_p(const void*, const void*, const void*, int, void*, void*, int, int64_t, int64_t,
-                              int64_t, hipStream_t);
-hipError_t madnn_linear_dgrad_p(const void*, const void*, const void*, void*, float*, int64_t, int64_t, int64_t, int,
-                                hipStream_t);
-hipError_t madnn_colsum_finalize(const float*, int, int64_t, void*, int, hipStream_t);
-hipError_t madnn_hwq_wait(const int*, int, int64_t, int*, hipStream_t);
-hipError_t madnn_hwq_set(int*, int, hipStream_t);
-hipError_t madnn_hwq_batch(const int*, const int*, int, int*, int*, int, int64_t, int*, const int*, hipStream_t);
-hipError_t madnn_hwq_spin(int64_t, hipStream_t);
-}
+#include "abi.h"
 
 namespace {
 
@@ -713,7 +573,7 @@ std::tuple<at::Tensor, at::Tensor> conv1x1_dgrad_bnb(const at::Tensor& dy, const
   at::Tensor dx = conv_out_like(dy, cin);
   at::Tensor part = at::empty({madnn_conv1x1_dgrad_rows(M, cin, cout), 2, cin}, dy.options().dtype(at::kFloat));
   check(madnn_conv1x1_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), nullptr, M, cin, cout, bny.data_ptr(), sc, sh,
-                            part.data_ptr<float>(), cur_stream(dy)),
+                            part.data_ptr<float>(), cur_stream(dy), nullptr),
         "conv1x1_dgrad_bnb");
   return {dx, part};
 }

@@ -21,6 +21,7 @@
 // launches per layer).
 #include <type_traits>
 
+#include "abi.h"
 #include "common.h"
 
 namespace madnn {
@@ -563,10 +564,6 @@ static int bn_grid_rows(int64_t M, int C) {
 
 extern "C" {
 
-// key 0: apply passes walk back to front (0/1), 1: apply workgroups per CU, 2: coefficient hoisting
-// (0/1), 4: reduction workgroups (partial rows) per CU; value < 0 only reads.
-// Key 4 sizes the partial slabs: change it only between steps (every call sizes its own workspace).
-// Returns the old value (-1 for an unknown key).
 int madnn_bn_tune(int key, int value) {
   int* f = key == 0   ? &madnn::bn_tune().reverse
            : key == 1 ? &madnn::bn_tune().wg_per_cu
@@ -586,12 +583,8 @@ int madnn_bn_supported(int C) { return (C % 8 == 0 && C >= 8 && C <= 2048) ? 1 :
 
 int madnn_bn_partial_rows(int64_t M, int C) { return madnn::bn_grid_rows(M, C); }
 
-// scratch floats the producer-partial paths need to fold many partial rows (prereduce)
 int madnn_bn_prereduce_floats(int C) { return madnn::kPreS * 2 * C; }
 
-// Forward. training: compute batch stats (+ running update); else use running stats.
-// ext_partial: [ext_rows][2][C] per-channel (sum, sum of squares) of x already produced by
-// the kernel that wrote x (K9 conv1x1 epilogue); the statistics pass over x is skipped.
 hipError_t madnn_bn_fwd(const void* x, const void* res, void* y, unsigned char* mask, int64_t M, int C, int xdt,
                         int relu, int training, float eps, float momentum, const float* w, const float* b,
                         float* run_mean, float* run_var, int64_t* nbt, float* save_mean, float* save_invstd,
@@ -631,8 +624,6 @@ hipError_t madnn_bn_fwd(const void* x, const void* res, void* y, unsigned char* 
   return hipGetLastError();
 }
 
-// The backward's reduction and finalize without the apply pass: dw / db and the per-channel coefficients
-// coef = ca | cb | cc of dx = ca g + cb x + cc ([3][C]), for a consumer that applies them itself (K9F).
 hipError_t madnn_bn_bwd_coef(const void* dy, const void* x, const unsigned char* mask, int has_res, int64_t M, int C,
                              int xdt, int relu, const float* w, const float* save_mean, const float* save_invstd,
                              const float* scale, const float* shift, float* dw, float* db, float* coef,
@@ -676,10 +667,6 @@ hipError_t madnn_bn_bwd(const void* dy, const void* x, const unsigned char* mask
 }
 
 
-// Training forward of relu(BN(x) + BN_r(r)): ResNet's last bottleneck BatchNorm with the downsample
-// path's BatchNorm folded into the same apply pass (bf16 only).  Each BN's statistics come from its
-// producer's epilogue (ext_partial*) or a statistics pass; both finalize into their own coefficients
-// and running statistics; one pass then writes y and the ReLU bit mask.
 hipError_t madnn_bn_fwd_dual(const void* x, const void* r, void* y, unsigned char* mask, int64_t M, int C,
                              float eps, float momentum, const float* w, const float* b, float* run_mean,
                              float* run_var, int64_t* nbt, float* save_mean, float* save_invstd, float* scale,
@@ -728,10 +715,6 @@ hipError_t madnn_bn_fwd_dual(const void* x, const void* r, void* y, unsigned cha
   return hipGetLastError();
 }
 
-// The dual backward's reduction and its two finalizes without the apply pass: dw / db of both BatchNorms and
-// coef = ca | cb | cc (dx = ca g + cb x + cc) followed by the residual BatchNorm's ca | cb | cc over r
-// ([6][C]), for consumers that apply them themselves (K9F on both convolutions of a downsample block).
-// workspace: bn_partial_rows(M, C) * 3 * C floats.
 hipError_t madnn_bn_bwd_dual_coef(const void* dy, const void* x, const void* r, const unsigned char* mask, int64_t M,
                                   int C, const float* w, const float* save_mean, const float* save_invstd,
                                   const float* w_r, const float* save_mean_r, const float* save_invstd_r, float* dw,
@@ -755,8 +738,6 @@ hipError_t madnn_bn_bwd_dual_coef(const void* dy, const void* x, const void* r, 
   return hipGetLastError();
 }
 
-// Backward of madnn_bn_fwd_dual: one reduction pass (sum g, sum g*x, sum g*r), two finalizes, one
-// apply pass writing dx and dr.  workspace: bn_partial_rows(M, C) * 3 * C floats; coef: 6 * C.
 hipError_t madnn_bn_bwd_dual(const void* dy, const void* x, const void* r, const unsigned char* mask, void* dx,
                              void* dr, int64_t M, int C, const float* w, const float* save_mean,
                              const float* save_invstd, const float* w_r, const float* save_mean_r,
@@ -776,7 +757,6 @@ hipError_t madnn_bn_bwd_dual(const void* dy, const void* x, const void* r, const
 }
 
 
-// Training statistics + finalize only (see bn_coef in binding.cpp): the apply runs in a consumer.
 hipError_t madnn_bn_coef(const void* x, int64_t M, int C, float eps, float momentum, const float* w, const float* b,
                          float* run_mean, float* run_var, int64_t* nbt, float* save_mean, float* save_invstd,
                          float* scale, float* shift, float* workspace, const float* ext_partial, int ext_rows,
@@ -801,7 +781,6 @@ hipError_t madnn_bn_coef(const void* x, int64_t M, int C, float eps, float momen
   return hipGetLastError();
 }
 
-// The backward finalize on its own (fused consumers with their own reduction pass: pool.hip)
 hipError_t madnn_bn_bwd_finalize(const float* partial, int G, int C, int pstride, int qoff, int64_t M, const float* w,
                                  const float* mean, const float* invstd, float* dw, float* db, float* ca, float* cb,
                                  float* cc, hipStream_t stream) {
@@ -811,9 +790,6 @@ hipError_t madnn_bn_bwd_finalize(const float* partial, int G, int C, int pstride
   return hipGetLastError();
 }
 
-// BatchNorm(+ReLU) backward whose reduction came from the producer of dy (K13's / K9's data-grad
-// epilogue: partial [G][2][C] = (sum g, sum g*x)): finalize + apply only.  coef: 3 * C floats.
-// scratch: madnn_bn_prereduce_floats(C) floats
 hipError_t madnn_bn_bwd_ext(const void* dy, const void* x, void* dx, int64_t M, int C, int relu, const float* w,
                             const float* save_mean, const float* save_invstd, const float* scale, const float* shift,
                             float* dw, float* db, float* coef, const float* partial, int G, float* scratch,

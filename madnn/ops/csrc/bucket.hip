@@ -14,6 +14,7 @@
 //    per-tensor chunk prefix maps blockIdx -> tensor (SGPR-only);
 //  * grid = total chunks (>> 256 CUs for any real bucket); scale by 1/W and the
 //    dtype cast are fused into the copy, so averaging costs no extra pass.
+#include "abi.h"
 #include "common.h"
 
 namespace madnn {

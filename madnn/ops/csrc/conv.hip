@@ -44,17 +44,8 @@
 // in round 6: docs/PERF.md.)
 #include <cstdlib>
 
+#include "abi.h"
 #include "mfma.h"
-
-// K12P (gemmp.hip): the deep forwards and the deep plain data grad run there (use_deep)
-extern "C" {
-int madnn_gemmp_supported(int64_t I, int64_t J, int64_t K, int has_bias);
-int madnn_conv1x1_fwd_p_rows(int64_t M, int64_t cout);
-hipError_t madnn_conv1x1_fwd_p(const void* x, const void* w, void* y, float* stats, int64_t M, int64_t cin,
-                               int64_t cout, hipStream_t s);
-hipError_t madnn_linear_dgrad_p(const void* dy, const void* w, const void* pre, void* dx, float* colsum, int64_t M,
-                                int64_t N, int64_t K, int gelu_kind, hipStream_t s);
-}
 
 namespace madnn {
 namespace conv {
@@ -1059,8 +1050,6 @@ using namespace madnn::conv;
 
 extern "C" {
 
-// key 0: forward/dgrad grid target, 1: weight-grad workgroups, 2: XCD remap (0/1), 3: ring main loop (0/1),
-// 4: deep forwards / plain data grad on K12P (0/1); returns the old value (value < 0: query only)
 int madnn_conv1x1_tune(int key, int value) {
   int* f = key == 0   ? &tune().fwd_wg
            : key == 1 ? &tune().wgrad_wg
@@ -1078,7 +1067,6 @@ int madnn_conv1x1_supported(int64_t cin, int64_t cout) {
   return (cin % 64 == 0 && cout % 64 == 0 && cin >= 64 && cout >= 64 && cin <= 16384 && cout <= 16384) ? 1 : 0;
 }
 
-// partial-statistics rows the forward writes ([rows][2][cout] fp32)
 int madnn_conv1x1_stat_rows(int64_t M, int64_t cin, int64_t cout) {
   if (!madnn_conv1x1_supported(cin, cout) || M <= 0) return 0;
   if (use_deep(M, cin, cout)) return madnn_conv1x1_fwd_p_rows(M, cout);
@@ -1087,7 +1075,6 @@ int madnn_conv1x1_stat_rows(int64_t M, int64_t cin, int64_t cout) {
   return p.j_groups;
 }
 
-// partial rows the BNB data grad writes ([rows][2][cin] fp32)
 int madnn_conv1x1_dgrad_rows(int64_t M, int64_t cin, int64_t cout) {
   if (!madnn_conv1x1_supported(cin, cout) || M <= 0) return 0;
   GemmArgs p{};
@@ -1126,10 +1113,6 @@ hipError_t madnn_conv1x1_fwd(const void* x, const void* w, void* y, float* stats
                : launch<false, false, 64, 128, kStoreT, false>(p, grid, s);
 }
 
-// dx = dY W (+ res: an accumulated gradient of the same layout, added in the epilogue)
-// bny/bnsc/bnsh/partial (optional, all or none): dx is d relu(bn(bny)); the epilogue also writes bn's
-// backward sums as partial [madnn_conv1x1_dgrad_rows][2][cin] (see BNB)
-// resmask (with res): res counts only where its ReLU bit is set
 hipError_t madnn_conv1x1_dgrad(const void* dy, const void* w, void* dx, const void* res, int64_t M, int64_t cin,
                                int64_t cout, const void* bny, const float* bnsc, const float* bnsh, float* partial,
                                hipStream_t s, const unsigned char* resmask) {
@@ -1169,7 +1152,6 @@ hipError_t madnn_conv1x1_dgrad(const void* dy, const void* w, void* dx, const vo
               : launch<true, false, 64, 128, kStoreT, false>(p, grid, s);
 }
 
-// fp32 floats of workspace madnn_conv1x1_wgrad needs (the per-split partial slabs)
 int64_t madnn_conv1x1_wgrad_ws(int64_t M, int64_t cin, int64_t cout) {
   int bi, bj, kc;
   int64_t tiles, splits;
@@ -1177,8 +1159,6 @@ int64_t madnn_conv1x1_wgrad_ws(int64_t M, int64_t cin, int64_t cout) {
   return splits * cin * cout;
 }
 
-// dw: [cout][cin] fp32 or (dw_bf16) bf16; ws: madnn_conv1x1_wgrad_ws floats (the per-split partial
-// slabs, summed in split order into dw -- one pass that also casts)
 hipError_t madnn_conv1x1_wgrad(const void* dy, const void* x, void* dw, int dw_bf16, float* ws, int64_t M, int64_t cin,
                                int64_t cout, hipStream_t s) {
   if (!madnn_conv1x1_supported(cin, cout)) return hipErrorInvalidValue;
@@ -1219,17 +1199,10 @@ hipError_t madnn_conv1x1_wgrad(const void* dy, const void* x, void* dw, int dw_b
   return hipGetLastError();
 }
 
-// K9F (bn3_conv3_bwd_kernel): the shapes it is built for
 int madnn_bn3_conv3_bwd_supported(int64_t c, int64_t c4) { return (c == kFC && c4 == kFC4) ? 1 : 0; }
 
-// workgroups = bn2 partial rows ([rows][2][C]) = dW3 slabs ([rows][4C][C] fp32 of workspace)
 int madnn_bn3_conv3_bwd_groups(int64_t M) { return M > 0 ? fused_groups(M) : 0; }
 
-// K9F launch.  y / coef / w / a: the BatchNorm input, its ca | cb | cc ([3][4C], bn_bwd_finalize_kernel), the
-// weight and the convolution input -- bn3's set (y3, W3, a2) or the downsample path's (yd, W_ds, xf).
-// y2 / sc2 / sh2 / partial all given: da is d relu(bn2(y2)) and partial gets bn2's backward sums (BNB); all
-// null: da is stored plainly.  partial / slabs: madnn_bn3_conv3_bwd_groups rows;
-// dw: [4C][C] fp32 or (dw_bf16) bf16, the slabs summed in workgroup order
 hipError_t madnn_bn3_conv3_bwd(const void* dout, const void* y, const unsigned char* mask, const float* coef,
                                const void* w, const void* a, const void* y2, const float* sc2, const float* sh2,
                                void* da, float* partial, float* slabs, void* dw, int dw_bf16, int64_t M, int64_t c,

@@ -30,6 +30,7 @@
 // [2][Cout] partial row per pixel tile (the input of bn.hip's finalize).
 #include <cstdlib>
 
+#include "abi.h"
 #include "mfma.h"
 
 namespace madnn {
@@ -489,8 +490,6 @@ int madnn_conv3x3_supported(int H, int W, int Ci, int Co) {
 
 int madnn_conv3x3_stat_rows(int64_t M) { return (int)((M + kBJ - 1) / kBJ); }
 
-// y = conv3x3(x, w) (stride 1, pad 1); x [N, H, W, Ci] NHWC, w [Co, 3, 3, Ci] (channels_last),
-// y [N, H, W, Co]; stats (optional): [ceil(M/256)][2][Co] partial sums of y
 hipError_t madnn_conv3x3_fwd(const void* x, const void* w, void* y, float* stats, int N, int H, int W, int Ci, int Co,
                              hipStream_t s) {
   if (!madnn_conv3x3_supported(H, W, Ci, Co)) return hipErrorInvalidValue;
@@ -520,8 +519,7 @@ hipError_t madnn_conv3x3_fwd(const void* x, const void* w, void* y, float* stats
   return hipGetLastError();
 }
 
-// Stride 2 (pad 1): x [N, H, W, Ci] with H, W even -> y [N, H/2, W/2, Co]; stats as above over the
-// output.  The halo is about twice as tall as at stride 1: one workgroup per CU at W = 56 (82 KiB).
+// Stride 2: the halo is about twice as tall as at stride 1: one workgroup per CU at W = 56 (82 KiB).
 int madnn_conv3x3_s2_supported(int H, int W, int Ci, int Co) {
   if (H < 2 || W < 2 || (H & 1) || (W & 1) || Ci % 64 || Co % 64 || Ci < 64 || Co < 64 || Ci > 8192) return 0;
   return conv3x3_lds(W, k13_ch(Ci), 2) <= 160 * 1024 ? 1 : 0;
@@ -558,8 +556,6 @@ hipError_t madnn_conv3x3_fwd_s2(const void* x, const void* w, void* y, float* st
   return hipGetLastError();
 }
 
-// Data grad with the BatchNorm-backward sums in the epilogue (see BNB): x = the output gradient,
-// w = the flipped / transposed weight, y = dx; partial [ceil(M/256)][2][Co] = (sum g, sum g*bny)
 hipError_t madnn_conv3x3_fwd_bnb(const void* x, const void* w, void* y, float* partial, const void* bny,
                                  const float* bnsc, const float* bnsh, int N, int H, int W, int Ci, int Co,
                                  hipStream_t s) {
@@ -624,7 +620,6 @@ int64_t madnn_conv3x3_wgrad_ws(int N, int H, int W, int Ci, int Co) {
   return (int64_t)p.splits * Co * 9 * Ci;
 }
 
-// dw [Co][3][3][Ci] (channels_last weight layout), fp32 (out_bf16 = 0) or bf16; ws: madnn_conv3x3_wgrad_ws floats
 hipError_t madnn_conv3x3_wgrad(const void* dy, const void* x, float* ws, void* dw, int out_bf16, int N, int H, int W,
                                int Ci, int Co, hipStream_t s) {
   WArgs p{};

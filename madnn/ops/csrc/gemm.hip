@@ -54,6 +54,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "abi.h"
 #include "k12.h"
 
 namespace madnn {
@@ -844,15 +845,12 @@ using namespace madnn::gemm;
 
 extern "C" {
 
-// Shapes K12 takes: reduction % 64 == 0, output features % 8 == 0, 16-B aligned rows, and
-// 32-bit-safe per-lane DMA offsets.
 int madnn_gemm_supported(int64_t I, int64_t J, int64_t K, int64_t lda, int64_t ldb) {
   if (I <= 0 || J <= 0 || K <= 0) return 0;
   if (K % kBK || I % 8 || lda % 8 || ldb % 8) return 0;
   return 1;
 }
 
-// Y[m][n] = X[m][k] W[n][k] (+ bias[n]) (-> gelu) (+ res[m][n]); aux (if given) = pre-activation
 hipError_t madnn_linear_fwd(const void* x, const void* w, const void* bias, int bias_f32, const void* res,
                             void* y, void* aux, int act, int64_t M, int64_t N, int64_t K, hipStream_t s) {
   if (!madnn_gemm_supported(N, M, K, K, K)) return hipErrorInvalidValue;
@@ -876,7 +874,6 @@ hipError_t madnn_linear_fwd(const void* x, const void* w, const void* bias, int 
   return launch(gemm_kernel<false, false>, kThreads, p, s);
 }
 
-// dX[m][k] = dY[m][n] W[n][k] (+ res[m][k]; res may alias dX for in-place accumulation)
 hipError_t madnn_linear_dgrad(const void* dy, const void* w, const void* res, void* dx, int64_t M, int64_t N,
                               int64_t K, hipStream_t s) {
   if (!madnn_gemm_supported(K, M, N, K, N)) return hipErrorInvalidValue;
@@ -916,8 +913,6 @@ int madnn_wgrad_splits(int64_t M, int64_t N, int64_t K) {
   return best;
 }
 
-// dW[n][k] (+)= sum_m dY[m][n] X[m][k] (bf16 out; with accumulate the existing dW is added).
-// ws: splits x N x K fp32 workspace when splits > 1 (madnn_wgrad_splits), else unused.
 hipError_t madnn_linear_wgrad(const void* dy, const void* x, void* dw, float* ws, int splits, int accumulate,
                               int64_t M, int64_t N, int64_t K, hipStream_t s) {
   if (M % kBK || !madnn_gemm_supported(K, N, M, K, N)) return hipErrorInvalidValue;

@@ -34,6 +34,7 @@
 // the kernel must have no scratch traffic (checked in the ISA by tests/test_gemm_gpu.py's build).
 #include <type_traits>
 
+#include "abi.h"
 #include "k12.h"
 
 namespace madnn {
@@ -483,7 +484,7 @@ __global__ __launch_bounds__(1024) void colsum_finalize_kernel(const float* __re
   }
 }
 
-int g_num_cus = 0;
+static int g_num_cus = 0;
 
 int num_cus() {
   if (g_num_cus == 0) {
@@ -517,8 +518,6 @@ using madnn::kGeluTanh;
 
 extern "C" {
 
-// Shapes K12P takes: output features and tokens multiples of 256 (no edge tiles), reduction a
-// multiple of 64, 32-bit-safe per-lane DMA offsets; a bias must fit the LDS bias slot.
 int madnn_gemmp_supported(int64_t I, int64_t J, int64_t K, int has_bias) {
   if (I <= 0 || J <= 0 || K <= 0) return 0;
   if (I % kT || J % kT || K % kBK) return 0;
@@ -528,8 +527,6 @@ int madnn_gemmp_supported(int64_t I, int64_t J, int64_t K, int has_bias) {
   return 1;
 }
 
-// Y[m][n] = X[m][k] W[n][k] (+ bias[n]); act 1 / 2 (tanh / erf GELU): aux = that pre-activation,
-// Y = gelu(aux)
 hipError_t madnn_linear_fwd_p(const void* x, const void* w, const void* bias, int bias_f32, void* y, void* aux,
                               int act, int64_t M, int64_t N, int64_t K, hipStream_t s) {
   if (!madnn_gemmp_supported(N, M, K, bias != nullptr) || (act != 0 && aux == nullptr) || act < 0 || act > 2)
@@ -552,10 +549,6 @@ hipError_t madnn_linear_fwd_p(const void* x, const void* w, const void* bias, in
                            : launch<false, kPlain>(p, s);
 }
 
-// The deep 1x1 convolution forward on NHWC rows, Y[m][co] = X[m][ci] W[co][ci] (no bias), with the
-// following BatchNorm's partial statistics: stats (or null: the plain kernel) gets
-// [madnn_conv1x1_fwd_p_rows][2][cout] fp32, one (sum, sum of squares) row pair per wave and tile
-// over the bf16-rounded outputs -- what K9's forward writes per workgroup (conv.hip header)
 int madnn_conv1x1_fwd_p_rows(int64_t M, int64_t cout) {
   (void)cout;
   return (int)(M / kT * 4);
@@ -578,9 +571,6 @@ hipError_t madnn_conv1x1_fwd_p(const void* x, const void* w, void* y, float* sta
   return stats != nullptr ? launch<false, kStats>(p, s) : launch<false, kPlain>(p, s);
 }
 
-// dX[m][k] = dY[m][n] W[n][k]; with pre: dX = that * gelu'(pre) (gelu_kind 1 tanh / 2 erf) and the
-// fp32 column sums of dX as
-// [M / 256 * 4][K] partial rows in colsum (madnn_colsum_finalize turns them into the bias grad)
 hipError_t madnn_linear_dgrad_p(const void* dy, const void* w, const void* pre, void* dx, float* colsum, int64_t M,
                                 int64_t N, int64_t K, int gelu_kind, hipStream_t s) {
   if (!madnn_gemmp_supported(K, M, N, 0) || (pre != nullptr && colsum == nullptr)) return hipErrorInvalidValue;

@@ -21,6 +21,7 @@
 //   accesses, both units' loads issued before the Philox rounds), one Philox call per unit.
 // Reference: none (SURVEY §2.5 lists the Llama config's model zoo, not these kernels); numerics are
 // checked against fp32 PyTorch in tests/test_glue_gpu.py.
+#include "abi.h"
 #include "common.h"
 #include "dropout.h"
 
@@ -193,8 +194,6 @@ using namespace madnn::glue;
 
 extern "C" {
 
-// src / dst: bf16 [rows = B*S][NH][D] contiguous (dst == src: in place, the NR rotated heads only);
-// heads 0..NR-1 rotated (q then k), the rest copied; cos / sin: fp32 [>= S][D]
 hipError_t madnn_rope_qkv(const void* src, void* dst, const float* cos_t, const float* sin_t, int64_t rows, int S,
                           int NH, int NR, int D, int inverse, hipStream_t st) {
   if (D % 16 || NR > NH || S <= 0 || rows % S) return hipErrorInvalidValue;
@@ -213,7 +212,6 @@ hipError_t madnn_rope_qkv(const void* src, void* dst, const float* cos_t, const 
   return hipGetLastError();
 }
 
-// gu: bf16 [M][2I], h: bf16 [M][I]; I % 8 == 0
 hipError_t madnn_swiglu_fwd(const void* gu, void* h, int64_t M, int I, hipStream_t st) {
   if (I % 8) return hipErrorInvalidValue;
   const int64_t units = M * (I / 8);
@@ -232,7 +230,6 @@ hipError_t madnn_swiglu_bwd(const void* dh, const void* gu, void* dgu, int64_t M
   return hipGetLastError();
 }
 
-// out = res + rp * m * x (res == nullptr: rp * m * x) on [rows][H] contiguous, dt = kF32 / kBF16, H % 8 == 0
 hipError_t madnn_dropout_add(const void* x, const void* res, void* out, int64_t rows, int H, int dt, uint32_t threshold,
                              uint64_t seed, uint64_t offset, hipStream_t st) {
   if (H <= 0 || H % 8 || threshold < 1 || threshold > 256 || (dt != madnn::kF32 && dt != madnn::kBF16))

@@ -23,6 +23,7 @@
 //    lane and chunk, half of its output used.
 #include <type_traits>
 
+#include "abi.h"
 #include "common.h"
 #include "dropout.h"
 
@@ -502,7 +503,6 @@ hipError_t madnn_norm_fwd(const void* x, const void* res, const void* w, const v
   return hipGetLastError();
 }
 
-// K3 DROP forward: sum_out = res + rp * m * x, y = norm(sum_out); threshold in 1..256 (see dropout.h)
 hipError_t madnn_norm_drop_fwd(const void* x, const void* res, const void* w, const void* b, void* y, void* sum_out,
                                float* mean_out, float* rstd_out, int64_t rows, int H, float eps, int rms, int xdt,
                                int wdt, uint32_t threshold, uint64_t seed, uint64_t offset, hipStream_t stream) {
@@ -535,7 +535,6 @@ static int64_t norm_bwd_groups(int64_t rows, int H) {
 
 int64_t madnn_norm_bwd_workspace(int64_t rows, int H) { return norm_bwd_groups(rows, H) * 3 * (int64_t)H; }
 
-// dsum (optional, [H], bf16 if dsum_bf16 else fp32): column sums of dx over the rows (norm_bwd_kernel CS)
 hipError_t madnn_norm_bwd(const void* dy, const void* x, const void* w, const float* mean_in, const float* rstd_in,
                           const void* dres, void* dx, void* dw, void* dbias, void* dsum, int dsum_bf16, float* workspace,
                           int64_t rows, int H, int rms, int xdt, int wdt, hipStream_t stream) {
@@ -565,7 +564,6 @@ hipError_t madnn_norm_bwd(const void* dy, const void* x, const void* w, const fl
   return hipGetLastError();
 }
 
-// K3 DROP backward: dx = dh (the residual's gradient), dx_drop = rp * m * dh; dsum: column sums of dx_drop
 hipError_t madnn_norm_drop_bwd(const void* dy, const void* x, const void* w, const float* mean_in, const float* rstd_in,
                                const void* dres, void* dx, void* dx_drop, void* dw, void* dbias, void* dsum,
                                int dsum_bf16, float* workspace, int64_t rows, int H, int rms, int xdt, int wdt,

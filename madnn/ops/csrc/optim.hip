@@ -10,6 +10,7 @@
 // 16-byte-per-lane vector accesses; grid = a few waves per CU, grid-stride.
 // An optional device-side scale (e.g. the clip coefficient produced by the
 // norm kernels below) multiplies the gradient without a host round trip.
+#include "abi.h"
 #include "common.h"
 
 namespace madnn {

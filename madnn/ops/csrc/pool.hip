@@ -13,6 +13,7 @@
 //             dx element is written exactly once: no memset, no atomics.
 // Tie-breaking/NaN follow ATen (first max in scan order; NaN wins).
 // Index math is 32-bit: the host refuses tensors with >= 2^31 elements.
+#include "abi.h"
 #include "common.h"
 
 namespace madnn {
@@ -501,8 +502,6 @@ int madnn_pool_bn_supported(int64_t numel, int C) {
   return numel < (1ll << 31) && C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0;
 }
 
-// maxpool_k3s2(relu(y * scale + shift)) (bf16 NHWC): output + 1-byte argmax per element; yarg (optional,
-// null = off): the raw input at each argmax, laid out as the output
 hipError_t madnn_pool_bn_fwd(const void* x, const float* scale, const float* shift, void* y, void* arg, void* yarg,
                              int N, int H, int W, int C, int Ho, int Wo, int p, hipStream_t stream) {
   if (!madnn_pool_bn_supported((int64_t)N * H * W * C, C) || p > 2) return hipErrorInvalidValue;
@@ -518,18 +517,11 @@ hipError_t madnn_pool_bn_fwd(const void* x, const float* scale, const float* shi
   return hipGetLastError();
 }
 
-hipError_t madnn_bn_bwd_finalize(const float* partial, int G, int C, int pstride, int qoff, int64_t M, const float* w,
-                                 const float* mean, const float* invstd, float* dw, float* db, float* ca, float* cb,
-                                 float* cc, hipStream_t stream);
-
-// partial rows the fused backward's reduction writes
 int madnn_pool_bn_bwd_rows(int64_t pixels, int C) {
   const int64_t work = pixels * (C / 8);
   return stream_grid(work, 256, g_pool_bn_wg[1] * kNumCU);  // gather-latency-bound: 8 workgroups per CU in flight
 }
 
-// dy (and the BN weight/bias grads) from the pool output gradient dp: reduction, finalize, apply.
-// workspace: madnn_pool_bn_bwd_rows * 2 * C floats; coef: 3 * C floats.
 hipError_t madnn_pool_bn_bwd(const void* dp, const void* arg, const void* y, const float* w, const float* mean,
                              const float* invstd, const float* scale, const float* shift, void* dy, float* dw,
                              float* db, float* coef, float* workspace, int N, int H, int W, int C, int Ho, int Wo,
@@ -549,12 +541,8 @@ hipError_t madnn_pool_bn_bwd(const void* dp, const void* arg, const void* y, con
   return hipGetLastError();
 }
 
-// partial rows the pooled-domain reduction writes (pooled = N * Hp * Wp pooled pixels)
 int madnn_pool_bn_bwd_pooled_rows(int64_t pooled, int C) { return stream_grid(pooled * (C / 8), 256, 8 * kNumCU); }
 
-// bn's weight/bias grads and backward coefficients (coef = ca, cb, cc: 3 * C floats) from the pool output
-// gradient dp and yarg, both [pooled][C] bf16: reduction + finalize.  pixels = N * H * W of bn's input.
-// workspace: madnn_pool_bn_bwd_pooled_rows * 2 * C floats.
 hipError_t madnn_pool_bn_bwd_pooled(const void* dp, const void* yarg, const float* w, const float* mean,
                                     const float* invstd, const float* scale, const float* shift, float* dw, float* db,
                                     float* coef, float* workspace, int64_t pooled, int64_t pixels, int C,

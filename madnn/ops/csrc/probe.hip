@@ -14,6 +14,7 @@
 // cannot start before the waiter gives up, and the waiter reports a timeout.
 // The wait is always bounded, so a blocked pair costs timeout_us and nothing
 // else (no unbounded spin can outlive the process).
+#include "abi.h"
 #include "common.h"
 
 namespace {

@@ -18,6 +18,7 @@
 //    the 14 A fragments of its wave's 32 channels (56 VGPRs), loaded once;
 //  * epilogue as K9: accumulators -> LDS [pixel][64] tile -> 16-byte stores (a tile's output row
 //    is one contiguous span), summing the bf16-rounded outputs per channel for the BatchNorm.
+#include "abi.h"
 #include "mfma.h"
 
 namespace madnn {
@@ -545,7 +546,6 @@ int madnn_stem_stat_rows(int N, int H, int W) {
   return stem_grid(N * Ho);
 }
 
-// x [N][H][W][3] bf16, wp packed [64][7][8][4] bf16 -> y [N][Ho][Wo][64]; stats [grid][2][64] or null
 hipError_t madnn_stem_fwd(const void* x, const void* wp, void* y, float* stats, int N, int H, int W, hipStream_t s) {
   if (!madnn_stem_supported(H, W)) return hipErrorInvalidValue;
   StemArgs a{};
@@ -571,13 +571,11 @@ hipError_t madnn_stem_fwd(const void* x, const void* wp, void* y, float* stats, 
   return hipGetLastError();
 }
 
-// fp32 workspace floats the weight gradient needs (per-workgroup partials)
 int64_t madnn_stem_wgrad_ws(int N, int H, int W) {
   const int Ho = (H + 6 - 7) / 2 + 1;
   return (int64_t)wgrad_grid(N * Ho) * kCo * 147;
 }
 
-// x [N][H][W][3], dy [N][Ho][Wo][64] bf16 -> dw [64][3][7][7] fp32 (ws: madnn_stem_wgrad_ws floats)
 hipError_t madnn_stem_wgrad(const void* x, const void* dy, float* ws, float* dw, int N, int H, int W,
                             hipStream_t s) {
   if (!madnn_stem_supported(H, W)) return hipErrorInvalidValue;
@@ -602,9 +600,6 @@ hipError_t madnn_stem_wgrad(const void* x, const void* dy, float* ws, float* dw,
   return hipGetLastError();
 }
 
-// The weight gradient with bn1's backward apply and the 3x3 / stride-2 max-pool's backward formed on chip:
-// y [N][Ho][Wo][64] the stem output, dp [N][Hp][Wp][64] the pool's output gradient, arg its argmax bytes
-// (pool.hip), scale/shift bn1's forward pair, ca/cb/cc its backward coefficients ([64] fp32 each).
 hipError_t madnn_stem_wgrad_bnp(const void* x, const void* y, const void* dp, const void* arg, const float* scale,
                                 const float* shift, const float* ca, const float* cb, const float* cc, float* ws,
                                 float* dw, int N, int H, int W, int p, hipStream_t s) {

@@ -14,6 +14,7 @@
 //             never slices/pads the logit matrix.
 // Rows need not be 16-byte aligned (V = 50257 is odd): each lane walks an
 // aligned vector body with a scalar head/tail.
+#include "abi.h"
 #include "common.h"
 
 namespace madnn {
@@ -296,7 +297,6 @@ __global__ __launch_bounds__(256) void xent_rescale_kernel(void* __restrict__ gr
 
 extern "C" {
 
-// chunks per lane the fused kernel needs for a row of ld 16-bit elements (0 = not supported)
 int madnn_xent_fused_chunks(int64_t ld) {
   if (ld % 8) return 0;
   const int64_t nch = ld / 8;

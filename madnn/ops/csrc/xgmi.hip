@@ -31,6 +31,8 @@
 #include <map>
 #include <mutex>
 
+#include "abi.h"
+
 namespace madnn {
 namespace xgmi {
 
@@ -187,8 +189,6 @@ extern "C" {
 int madnn_oneshot_max_peers() { return kMaxPeers; }
 int madnn_oneshot_handle_bytes() { return (int)sizeof(hipIpcMemHandle_t); }
 
-// Allocate this rank's staging buffer (2 x cap bytes) and uncached flag array, and return their
-// IPC handles (2 x handle_bytes into `handles`).  Returns the context id (> 0) or -hipError.
 int madnn_oneshot_create(int64_t cap, int world, int rank, int device, unsigned char* handles) {
   if (world < 1 || world > kMaxPeers || rank < 0 || rank >= world || cap <= 0) return -(int)hipErrorInvalidValue;
   Ctx c;
@@ -225,7 +225,6 @@ int madnn_oneshot_create(int64_t cap, int world, int rank, int device, unsigned 
   return id;
 }
 
-// Map every peer's buffers: all_handles = world x (2 x handle_bytes), rank-major.
 int madnn_oneshot_open(int id, const unsigned char* all_handles) {
   std::lock_guard<std::mutex> g(mu());
   auto it = ctxs().find(id);
@@ -253,9 +252,6 @@ int madnn_oneshot_open(int id, const unsigned char* all_handles) {
   return (int)e;
 }
 
-// out = sum over ranks of in (n elements, dtype 0 fp32 / 1 bf16; in/out may alias).  Every rank
-// must call with the same n and dtype, in the same order.  Asynchronous on `stream`; a peer that
-// never arrives sets the context's error word (madnn_oneshot_error) instead of hanging the GPU.
 int madnn_oneshot_allreduce(int id, const void* in, void* out, int64_t n, int dtype, int spin_limit,
                             hipStream_t stream) {
   Args a{};
@@ -288,9 +284,6 @@ int madnn_oneshot_allreduce(int id, const void* in, void* out, int64_t n, int dt
   return (int)hipGetLastError();
 }
 
-// error word of the context (1 = a wait timed out).  flags bit 0: clear it after reading;
-// bit 1: synchronise the device first (otherwise the word reflects the kernels that have
-// finished so far -- a plain host read of pinned memory, no stall)
 int madnn_oneshot_error(int id, int flags) {
   std::lock_guard<std::mutex> g(mu());
   auto it = ctxs().find(id);

@@ -168,10 +168,10 @@ _VARIANTS = [(7, 0), (8, 0)]
 @pytest.mark.parametrize("key,value", _VARIANTS)
 @pytest.mark.parametrize("B,S,H,HKV,D,causal", [(1, 256, 4, 2, 64, True), (2, 192, 2, 2, 64, False)])
 def test_attention_tunable_variants_match_reference(cuda, key, value, B, S, H, HKV, D, causal):
-    import ctypes
+    import functools
 
     assert ops.load_kernels()
-    knob = ctypes.CDLL(str(ops.kernels_path())).madnn_attn_tune
+    knob = functools.partial(ops.native_tune, "attn")
     old = knob(key, value)
     assert old >= 0
     try:

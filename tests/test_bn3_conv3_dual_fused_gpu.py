@@ -9,7 +9,7 @@ most 1.5x the unfused path's, and at most 2x that of an eager emulation of the b
 forward; dy3, dyd, da2 backward).  Two runs of the fused path are bitwise equal.  Every test prints the
 measured errors (``pytest -s``).
 """
-import ctypes
+import functools
 
 import pytest
 import torch
@@ -156,7 +156,7 @@ def test_dual_fused_matches_fp32_and_unfused(cuda, monkeypatch, shape):
 
 def test_dual_fused_many_tiles_per_workgroup(cuda, monkeypatch):
     """M = 3136 = 24.5 tiles on 3 workgroups: each walks 8-9 tiles carrying dW, and three slabs are summed."""
-    tune = ctypes.CDLL(str(ops.kernels_path())).madnn_conv1x1_tune
+    tune = functools.partial(ops.native_tune, "conv1x1")
     old = tune(0, 3)
     try:
         _check((4, 64, 256, 28, 28), cuda, monkeypatch, seed=1)

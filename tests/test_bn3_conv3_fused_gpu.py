@@ -6,7 +6,7 @@ Both paths round dy3 to bf16 at the same point and accumulate in fp32, so only s
 the fused path's relative error against fp32 may be at most 1.5x the unfused path's.  Every test prints
 the measured errors (``pytest -s``).
 """
-import ctypes
+import functools
 
 import pytest
 import torch
@@ -164,7 +164,7 @@ def test_fused_matches_fp32_and_unfused(cuda, monkeypatch, shape):
 
 def test_fused_many_tiles_per_workgroup(cuda, monkeypatch):
     """M = 3136 = 24.5 tiles on 3 workgroups: each walks 8-9 tiles and carries dW3 across them."""
-    tune = ctypes.CDLL(str(ops.kernels_path())).madnn_conv1x1_tune
+    tune = functools.partial(ops.native_tune, "conv1x1")
     old = tune(0, 3)
     try:
         _check((4, 64, 256, 28, 28), cuda, monkeypatch, seed=1)

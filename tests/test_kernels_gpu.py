@@ -654,11 +654,11 @@ def test_batchnorm_apply_walk_variants_bitwise(cuda):
     """The BN apply walks with and without coefficient hoisting (the per-chunk reload is also the
     path for grid strides that are not a multiple of C) are pure scheduling changes: outputs and
     gradients must be bitwise identical."""
-    import ctypes
+    import functools
 
     from madnn.nn.norm import FusedBatchNorm2d
 
-    tune = ctypes.CDLL(str(ops.kernels_path())).madnn_bn_tune
+    tune = functools.partial(ops.native_tune, "bn")
     torch.manual_seed(12)
     C = 256
     x = torch.randn(16, C, 56, 56, device=cuda).bfloat16().contiguous(memory_format=torch.channels_last)
