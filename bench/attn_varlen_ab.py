@@ -21,6 +21,15 @@ itself.  The result holds, per shape, the medians, all rounds of every arm, the 
 over the rounds) of (a), the ratio (b) / (a) and whether (c) - (b) exceeds that spread.
 
     python bench/attn_varlen_ab.py [--batch 32] [--rounds 7] [--out profiles/attn_varlen_ab.json]
+
+``--segments DOC`` times packed rows instead (the SEG kernels; GPT-2 medium's and Llama-3 8B's shapes): every
+row is S / DOC documents of DOC tokens.  Arms: (a) dense as above -- documents attending across their
+boundaries; (b) ``seg``, ops.attention(segments=bounds); ``one``, the same rows declared ONE document (the SEG
+kernels walking every tile: what the two limits cost); (c) ``sdpa`` with the block-diagonal mask, which is what
+reference.attention gives such a batch and all a packed batch could run before.  (b) is compared with (c) on
+every row.  ``tile_fraction``: the 64 x 64 score tiles that meet a document over those dense K8 walks.
+
+    python bench/attn_varlen_ab.py --segments 512 --out profiles/attn_segments_ab.json
 """
 from __future__ import annotations
 
@@ -41,7 +50,7 @@ SHAPES = {  # name: (S, H, Hkv, D, causal, batch or None for --batch, divisor of
 }
 
 
-def child(name: str, batch: int, rounds: int, iters: int) -> dict:
+def child(name: str, batch: int, rounds: int, iters: int, doc: int = 0) -> dict:
     import torch
     import torch.nn.functional as F
 
@@ -64,6 +73,11 @@ def child(name: str, batch: int, rounds: int, iters: int) -> dict:
     if causal:
         mask = mask & torch.ones(S, S, dtype=torch.bool, device="cuda").tril()
     mask = mask.contiguous()
+    if doc:   # packed rows: equal documents of `doc` tokens; every row valid
+        bounds = ops.segment_bounds((torch.arange(S, device="cuda") // doc).expand(B, S))
+        one = ops.segment_bounds(torch.zeros(B, S, dtype=torch.int32, device="cuda"))
+        mask = reference.attention_segments_mask(bounds, causal).contiguous()
+        valid = torch.ones_like(valid)
 
     def dense():
         return ops.attention(q, k, v, causal=causal)
@@ -79,6 +93,10 @@ def child(name: str, batch: int, rounds: int, iters: int) -> dict:
     tune = functools.partial(ops.native_tune, "attn")
 
     arms = {"dense": dense, "varlen": varlen, "sdpa": sdpa, "staged": dense}
+    if doc:   # "varlen" is the arm under test in the shared report below
+        varlen = lambda: ops.attention(q, k, v, causal=causal, segments=bounds)
+        arms = {"dense": dense, "varlen": varlen, "sdpa": sdpa, "staged": dense,
+                "one": lambda: ops.attention(q, k, v, causal=causal, segments=one)}
 
     def step(fn):
         torch.autograd.grad(fn(), (q, k, v), do)
@@ -118,6 +136,20 @@ def child(name: str, batch: int, rounds: int, iters: int) -> dict:
             ts[arm].append(timeit(arm))
     med = {arm: statistics.median(t) for arm, t in ts.items()}
     spread = max(ts["dense"]) - min(ts["dense"])
+    if doc:   # packed rows: the arm under test is reported as "seg", none of the padded-batch fields apply
+        n, m = S // 64, doc // 64
+        frac = (S // doc) * (m * (m + 1) / 2 if causal else m * m) / (n * (n + 1) / 2 if causal else n * n)
+        ts["seg"], med["seg"] = ts.pop("varlen"), med.pop("varlen")
+        return {"shape": name, "B": B, "S": S, "H": H, "Hkv": HKV, "D": D, "causal": causal, "rounds": rounds,
+                "iters_per_round": iters, "doc_tokens": doc, "tile_fraction": round(frac, 4),
+                "fwd_bwd_us": {arm: round(x, 1) for arm, x in med.items()},
+                "rounds_us": {arm: [round(x, 1) for x in t] for arm, t in ts.items()},
+                "dense_spread_us": round(spread, 1), "seg_over_dense": round(med["seg"] / med["dense"], 4),
+                "seg_over_staged": round(med["seg"] / med["staged"], 4),
+                "one_document_over_dense": round(med["one"] / med["dense"], 4),
+                "sdpa_over_seg": round(med["sdpa"] / med["seg"], 4),
+                "seg_faster_than_sdpa_by_more_than_spread": med["sdpa"] - med["seg"] > spread,
+                "seg_vs_sdpa_rel_err": agree}
     return {"shape": name, "B": B, "S": S, "H": H, "Hkv": HKV, "D": D, "causal": causal, "rounds": rounds,
             "iters_per_round": iters, "mean_len_over_S": round(float(lens.float().mean()) / S, 4),
             "valid_tile_fraction": round(float((lens.float() ** 2).mean()) / S ** 2, 4),
@@ -137,15 +169,19 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per shape (one child process each)")
     ap.add_argument("--out", default="profiles/attn_varlen_ab.json")
+    ap.add_argument("--segments", type=int, default=0, metavar="DOC",
+                    help="packed rows of DOC-token documents (a multiple of 64 dividing S) instead of padded ones")
     ap.add_argument("--child", choices=sorted(SHAPES), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(child(a.child, a.batch, a.rounds, a.iters)), flush=True)
+        print(json.dumps(child(a.child, a.batch, a.rounds, a.iters, a.segments)), flush=True)
         return 0
     rows = []
     for name in SHAPES:
+        if a.segments and name == "bert-large":
+            continue
         cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--batch", str(a.batch), "--rounds",
-               str(a.rounds), "--iters", str(a.iters)]
+               str(a.rounds), "--iters", str(a.iters), "--segments", str(a.segments)]
         try:
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
         except subprocess.TimeoutExpired:

@@ -66,9 +66,12 @@ def _only_implicit_offset(pstream, bstream, grown_by, parent_hash):
     return moved
 
 
-def _is_varlen(key):
+def _is_new_instantiation(key, extra):
+    """An expected new kernel: an instantiation of a grown template with its NEW (last) flag set (VARLEN, or SEG one
+    parameter later), or a kernel named by ``--new-kernel``."""
     m = re.match(r"^attn\.hip: void (\w+)<([^>]*)>", key)
-    return bool(m and m.group(1) in GROWN and m.group(2).split(", ")[-1] == "true" and len(m.group(2).split(", ")) == 4)
+    return any(re.search(rf"\b{re.escape(n)}\b", key) for n in extra) or bool(
+        m and m.group(1) in GROWN and m.group(2).split(", ")[-1] == "true" and len(m.group(2).split(", ")) >= 4)
 
 
 def main():
@@ -78,6 +81,9 @@ def main():
     ap.add_argument("--parent-asm", help="the parent dump's --keep-asm directory")
     ap.add_argument("--branch-asm", help="the branch dump's --keep-asm directory")
     ap.add_argument("--grown-by", type=int, default=8, help="bytes the explicit argument block grew by")
+    ap.add_argument("--new-key", default="varlen_instantiations", help="the record's name for the new kernels")
+    ap.add_argument("--new-kernel", action="append", default=[], metavar="NAME",
+                    help="a kernel the change adds besides the new instantiations (repeatable)")
     ap.add_argument("--out")
     args = ap.parse_args()
     pa, br = json.loads(Path(args.parent).read_text()), json.loads(Path(args.branch).read_text())
@@ -105,7 +111,7 @@ def main():
     new = {k: {"vgpr_count": v["vgpr_count"], "scratch": v["private_segment_fixed_size"],
                "lds": v["group_segment_fixed_size"], "instructions": v["instructions"]}
            for k, v in sorted(br.items()) if k not in paired}
-    not_varlen = [k for k in new if not _is_varlen(k)]
+    not_varlen = [k for k in new if not _is_new_instantiation(k, args.new_kernel)]
     bad = {k: v for k, v in new.items() if v["scratch"] != 0 or (
         re.search(r"attn_(fwd|bwd_dq)_kernel<128", k) and v["vgpr_count"] > 256)}
     for k in missing:
@@ -113,7 +119,7 @@ def main():
     for k, d in differ.items():
         print(f"DIFFERS: {k}\n  parent {d['parent']}\n  branch {d['branch']}")
     for k in not_varlen:
-        print(f"ERROR: new kernel that is no VARLEN instantiation: {k}")
+        print(f"ERROR: unexpected new kernel: {k}")
     for k, v in new.items():
         print(f"new: {k}: {v}")
     for k, v in bad.items():
@@ -131,7 +137,7 @@ def main():
                     "in the stream, and no VGPR count, LDS footprint or scratch size, changed",
             "attn_hip_identical": [r for r in identical if r["parent"].startswith("attn.hip: ")],
             "attn_hip_same_up_to_implicit_argument_offset": moved_only,
-            "varlen_instantiations": new}, indent=1))
+            args.new_key: new, "new_with_scratch_or_over_256_vgprs_at_d128_fwd_dq": sorted(bad)}, indent=1))
     return 1 if differ or missing or not_varlen or bad else 0
 
 

@@ -62,23 +62,25 @@ class SelfAttention(nn.Module):
         self.qkv = nn.Linear(hidden, (heads + 2 * self.kv_heads) * self.head_dim, bias=bias)
         self.proj = nn.Linear(heads * self.head_dim, hidden, bias=bias)
 
-    def forward(self, x: torch.Tensor, seqlens=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, seqlens=None, segments=None) -> torch.Tensor:
         """``seqlens`` (int32 [B] on x's device, optional): a right-padded batch, the contract of
         :func:`ops.attention` -- valid rows attend to their sequence's valid keys only, the attention
-        output of padded rows is zero (the output projection then leaves its bias there)."""
+        output of padded rows is zero (the output projection then leaves its bias there).
+        ``segments`` (document ids [B, S] or their :func:`ops.segment_bounds`, optional; not with
+        ``seqlens``): packed rows, every token attends inside its own document only."""
         b, s, _ = x.shape
-        return self.attend(linear(self.qkv, x), b, s, seqlens)
+        return self.attend(linear(self.qkv, x), b, s, seqlens, segments)
 
-    def forward_tee(self, x: torch.Tensor, seqlens=None):
+    def forward_tee(self, x: torch.Tensor, seqlens=None, segments=None):
         """``(attn(x), x')``: the QKV projection through :func:`ops.linear_tee`, so a residual path
         that uses ``x'`` has its gradient summed inside the projection's data-gradient GEMM."""
         b, s, _ = x.shape
         if ops.FUSED_LINEAR and type(self.qkv) is nn.Linear:
             qkv, xr = ops.linear_tee(x, self.qkv.weight, self.qkv.bias)
-            return self.attend(qkv, b, s, seqlens), xr
-        return self.forward(x, seqlens), x
+            return self.attend(qkv, b, s, seqlens, segments), xr
+        return self.forward(x, seqlens, segments), x
 
-    def attend(self, qkv: torch.Tensor, b: int, s: int, seqlens=None) -> torch.Tensor:
+    def attend(self, qkv: torch.Tensor, b: int, s: int, seqlens=None, segments=None) -> torch.Tensor:
         """Attention and the output projection on the QKV projection's output ``[b, s, (H + 2 Hkv) D]``."""
         qkv = qkv.view(b, s, self.heads + 2 * self.kv_heads, self.head_dim)
         drop = self.dropout if self.training else 0.0
@@ -89,7 +91,7 @@ class SelfAttention(nn.Module):
                 # K14: q and k rotated in one pass into a packed buffer (backward: in place on dQKV)
                 qkv = ops.rope_qkv(qkv.contiguous(), self.rope.cos, self.rope.sin, self.heads + self.kv_heads)
             o = ops.attention_qkvpacked(qkv, self.heads, self.kv_heads, causal=self.causal, dropout_p=drop,
-                                        seqlens=seqlens)
+                                        seqlens=seqlens, segments=segments)
             return linear(self.proj, o.view(b, s, self.heads * self.head_dim))
         q, k, v = qkv.split([self.heads, self.kv_heads, self.kv_heads], dim=2)
         q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
@@ -97,6 +99,12 @@ class SelfAttention(nn.Module):
             q, k = self.rope(q, k)
         gqa = self.kv_heads != self.heads
         mask = valid = None
+        if segments is not None:
+            # packed rows: the block-diagonal mask of the documents (reference.attention)
+            if seqlens is not None:
+                raise ValueError("attention: segments and seqlens exclude each other")
+            mask = ops.reference.attention_segments_mask(
+                ops.reference._segments_bounds(segments.to(qkv.device), b, s), self.causal)
         if seqlens is not None:
             # the same contract as K8's: padded positions replaced by zeros (select), valid rows see the
             # valid keys, padded rows of the output are zeros (reference.attention)

@@ -76,9 +76,10 @@ class LlamaBlock(nn.Module):
         self.post_attn_norm = FusedRMSNorm(cfg.hidden, eps=cfg.rms_eps)
         self.mlp = LlamaMLP(cfg)
 
-    def forward(self, x):
+    def forward(self, x, segments=None):
+        """``segments``: packed rows (see :meth:`Llama.forward`), handed to the attention."""
         y, xr = self.input_norm(x, fork=True)  # residual path's gradient joins the norm's backward
-        a = self.attn(y)
+        a = self.attn(y, segments=segments)
         y, h = self.post_attn_norm(a, residual=xr)
         return self.mlp(y, residual=h)
 
@@ -103,10 +104,20 @@ class Llama(nn.Module):
         self.head = LlamaHead(cfg)
         init_normal_(self)
 
-    def forward(self, ids):
+    def forward(self, ids, segments=None):
+        """``segments`` (integer document ids [B, S], or their :func:`ops.segment_bounds`): packed rows --
+        several documents concatenated in one row, every token attending inside its own document only.
+        The bounds are computed once here and shared by all layers.  RoPE is relative: a score depends on
+        the distance between query and key only, so it does not matter where in the row a document
+        starts and no per-document position reset is needed.  (Not threaded through
+        :meth:`pipeline_layers`, like ``seqlens``.)"""
         x = self.embed(ids)
+        if segments is not None and segments.dim() == 2:
+            segments = ops.segment_bounds(segments.to(ids.device))
         for blk in self.layers:
-            x = blk(x)
+            # one positional argument without segments: wrappers and hooks around the blocks (checkpointing, the
+            # pipeline stages' forward spies in the tests) are written for blk(x)
+            x = blk(x) if segments is None else blk(x, segments)
         return self.head(x)
 
     @staticmethod

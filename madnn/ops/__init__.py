@@ -695,20 +695,21 @@ class _AttnFn(torch.autograd.Function):
     """q [B,S,H,D], k/v [B,S,Hkv,D] (strided views) -> o [B,S,H,D] contiguous."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, p=0.0, seed=0, offset=0, seqlens=None):
-        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset, seqlens)
-        ctx.save_for_backward(q, k, v, o, lse, seqlens)   # seqlens (or None) stays on the device: no host sync
+    def forward(ctx, q, k, v, causal, scale, p=0.0, seed=0, offset=0, seqlens=None, segments=None):
+        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset, seqlens, segments)
+        # seqlens / the segment bounds (or None) stay on the device: no host sync
+        ctx.save_for_backward(q, k, v, o, lse, seqlens, segments)
         ctx.causal, ctx.scale = causal, scale
         ctx.drop = (p, seed, offset)   # the backward kernels regenerate the mask from these
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, seqlens = ctx.saved_tensors
+        q, k, v, o, lse, seqlens, segments = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, float(ctx.scale), None, *ctx.drop,
-                                 seqlens)
-        return dq, dk, dv, None, None, None, None, None, None
+                                 seqlens, segments)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 class _AttnPackedFn(torch.autograd.Function):
@@ -716,10 +717,10 @@ class _AttnPackedFn(torch.autograd.Function):
     into one buffer (no split/cat copies in either direction)."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, kv_heads, causal, scale, p=0.0, seed=0, offset=0, seqlens=None):
+    def forward(ctx, qkv, heads, kv_heads, causal, scale, p=0.0, seed=0, offset=0, seqlens=None, segments=None):
         q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
-        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset, seqlens)
-        ctx.save_for_backward(qkv, o, lse, seqlens)
+        o, lse = torch.ops.madnn.attn_fwd(q, k, v, bool(causal), float(scale), p, seed, offset, seqlens, segments)
+        ctx.save_for_backward(qkv, o, lse, seqlens, segments)
         ctx.meta = (heads, kv_heads, bool(causal), float(scale))
         ctx.drop = (p, seed, offset)
         # qkv is (a view of) a biased madnn Linear's output: the backward kernels also sum dQKV's
@@ -730,7 +731,7 @@ class _AttnPackedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse, seqlens = ctx.saved_tensors
+        qkv, o, lse, seqlens, segments = ctx.saved_tensors
         heads, kv_heads, causal, scale = ctx.meta
         q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
         dqkv = torch.empty_like(qkv)
@@ -738,10 +739,10 @@ class _AttnPackedFn(torch.autograd.Function):
         cs = None
         if ctx.colsum:
             cs = torch.empty((heads + 2 * kv_heads) * qkv.size(-1), dtype=ctx.colsum_dtype, device=qkv.device)
-        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cs, *ctx.drop, seqlens)
+        torch.ops.madnn.attn_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, cs, *ctx.drop, seqlens, segments)
         if cs is not None:
             _attach(dqkv, "_madnn_colsum", cs)
-        return dqkv, None, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None, None
 
 
 ATTN_COLSUM = os.environ.get("MADNN_ATTN_COLSUM", "1") != "0"  # A/B switch (see _AttnPackedFn.forward)
@@ -798,8 +799,50 @@ def _seqlens_arg(seqlens, like: torch.Tensor):
     return seqlens.to(device=like.device, dtype=torch.int32).contiguous()
 
 
+def segment_bounds(ids: torch.Tensor) -> torch.Tensor:
+    """int32 [B, 2, S] document bounds of packed rows from integer document ids [B, S]: a document is a
+    maximal run of equal consecutive ids (ids need not be sorted or unique), ``[:, 0, s]`` the index of
+    the first token of token s's document and ``[:, 1, s]`` one past its last.  Pass the result as
+    ``segments=`` so that a model scans once per forward, not once per layer.  On the device: one launch
+    of a K8 kernel (ids are compared as int32 values); on the CPU: :func:`reference.segment_bounds`."""
+    if _is_dev(ids):
+        _need_native("segment_bounds")
+        if ids.dim() != 2 or ids.is_floating_point() or ids.dtype == torch.bool:
+            raise ValueError(f"segment ids must be an integer [B, S] tensor, got {tuple(ids.shape)} {ids.dtype}")
+        return torch.ops.madnn.segment_bounds(ids)
+    return reference.segment_bounds(ids)
+
+
+def _segments_arg(segments, like: torch.Tensor, seqlens, native: bool):
+    """``segments`` as the kernels take it: None, or contiguous int32 bounds [B, 2, S] on ``like``'s
+    device -- ids [B, S] are scanned, bounds are taken as they are.  Values are never read on the host.
+    ``native``: the call goes to K8, so ids are scanned by :func:`segment_bounds` (its kernel on the
+    device); a call bound for :func:`reference.attention` scans with :func:`reference.segment_bounds` and
+    needs no kernel library."""
+    if segments is None:
+        return None
+    if seqlens is not None:
+        raise ValueError("attention: segments and seqlens exclude each other (a padded tail is a document of its own)")
+    B, S = like.size(0), like.size(1)
+    segments = segments.to(like.device)
+    if segments.dim() == 2 and tuple(segments.shape) == (B, S):
+        return segment_bounds(segments) if native else reference.segment_bounds(segments)
+    if segments.dim() == 3 and tuple(segments.shape) == (B, 2, S) and not segments.is_floating_point():
+        return segments.to(torch.int32).contiguous()
+    raise ValueError(f"segments must be integer ids [B = {B}, S = {S}] or bounds [B, 2, S], got "
+                     f"{tuple(segments.shape)} {segments.dtype}")
+
+
+def _seg_tail(segments) -> tuple:
+    """The bounds as the trailing argument of ``_AttnFn`` / ``_AttnPackedFn.apply``: passed only when
+    given, so a call without segments is the call it was before the argument existed
+    (tests/test_attention_varlen_gpu.py::test_zoo_bert_padded_batch_matches_per_sequence_fp32 and
+    tests/test_hf_varlen_gpu.py spy on ``apply`` and read ``seqlens`` as its last positional argument)."""
+    return () if segments is None else (segments,)
+
+
 def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dropout_p: float = 0.0, rng=None,
-              seqlens=None):
+              seqlens=None, segments=None):
     """Scaled-dot-product attention on [B, S, heads, D] tensors (GQA when k/v have fewer heads).
     Returns [B, S, H, D].  HIP bf16 inputs run K8; anything else runs SDPA.  ``dropout_p`` drops
     attention probabilities (K8: in-kernel mask, see :func:`reference.attention_dropout_mask`);
@@ -814,29 +857,50 @@ def attention(q, k, v, *, causal: bool = True, scale: Optional[float] = None, dr
     query rows of the output are exact zeros and so are the gradients at padded positions of q, k and
     v; nothing stored at a padded position of q, k, v or the incoming gradient reaches a result (NaN
     there does not propagate).  K8 skips the key tiles and query blocks past ``L_b``.  The dropout
-    mask stays the same function of the absolute (b, h, q, k).  ``seqlens=None``: every position valid."""
+    mask stays the same function of the absolute (b, h, q, k).  ``seqlens=None``: every position valid.
+
+    ``segments`` (integer document ids [B, S] on the inputs' device, or their :func:`segment_bounds`
+    [B, 2, S]) declares packed rows: several documents concatenated in one row, a document being a
+    maximal run of equal consecutive ids.  Query ``q`` attends to the keys of its own document only,
+    ``lo[b, q] <= k < hi[b, q]`` (and ``k <= q`` when causal), as if each document ran alone; every row
+    sees at least itself, so the LSE is finite everywhere.  K8 walks only the tiles a block's documents
+    reach; the values are never read on the host (no sync, graph-capturable).  Out of scope:
+    ``segments`` with ``seqlens`` raises ``ValueError`` (a padded tail is simply a document of its own,
+    which the loss ignores); ``segments`` with ``dropout_p > 0``, or with a dtype, head dim or scale K8
+    does not take, runs :func:`reference.attention` (a materialised block-diagonal mask into SDPA).
+    ``segments=None`` changes nothing."""
     scale = scale if scale is not None else q.size(-1) ** -0.5
     seqlens = _seqlens_arg(seqlens, q)
-    if attention_supported(q, q.size(-1), dropout_p) and _attn_scale_ok(scale):
+    native = (attention_supported(q, q.size(-1), dropout_p) and _attn_scale_ok(scale)
+              and (segments is None or dropout_p == 0.0))
+    segments = _segments_arg(segments, q, seqlens, native)
+    if native:
         _need_native("attention")
-        return _AttnFn.apply(q, k, v, causal, scale, *_dropout_args(q, dropout_p, rng), seqlens)
-    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p, seqlens=seqlens)
+        return _AttnFn.apply(q, k, v, causal, scale, *_dropout_args(q, dropout_p, rng), seqlens, *_seg_tail(segments))
+    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p, seqlens=seqlens,
+                               segments=segments)
 
 
 def attention_qkvpacked(qkv, heads: int, kv_heads: int, *, causal: bool = True, scale: Optional[float] = None,
-                        dropout_p: float = 0.0, rng=None, seqlens=None):
+                        dropout_p: float = 0.0, rng=None, seqlens=None, segments=None):
     """Attention straight from a packed projection ``qkv`` [B, S, heads + 2*kv_heads, D]
-    (``dropout_p`` / ``rng`` / ``seqlens`` as in :func:`attention`; a ``scale`` that is not finite and
-    positive runs :func:`reference.attention`, as there).  With ``seqlens`` the column sums handed to a
-    biased projection as its bias gradient cover the valid rows only (the padded rows of dQKV are zeros)."""
+    (``dropout_p`` / ``rng`` / ``seqlens`` / ``segments`` as in :func:`attention`; a ``scale`` that is not
+    finite and positive runs :func:`reference.attention`, as there).  With ``seqlens`` the column sums handed
+    to a biased projection as its bias gradient cover the valid rows only (the padded rows of dQKV are zeros);
+    with ``segments`` every row is valid and they cover all rows."""
     d = qkv.size(-1)
     scale = scale if scale is not None else d ** -0.5
     seqlens = _seqlens_arg(seqlens, qkv)
-    if attention_supported(qkv, d, dropout_p) and qkv.is_contiguous() and _attn_scale_ok(scale):
+    native = (attention_supported(qkv, d, dropout_p) and qkv.is_contiguous() and _attn_scale_ok(scale)
+              and (segments is None or dropout_p == 0.0))
+    segments = _segments_arg(segments, qkv, seqlens, native)
+    if native:
         _need_native("attention")
-        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_dropout_args(qkv, dropout_p, rng), seqlens)
+        return _AttnPackedFn.apply(qkv, heads, kv_heads, causal, scale, *_dropout_args(qkv, dropout_p, rng), seqlens,
+                                   *_seg_tail(segments))
     q, k, v = qkv.split([heads, kv_heads, kv_heads], dim=2)
-    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p, seqlens=seqlens)
+    return reference.attention(q, k, v, causal=causal, scale=scale, dropout_p=dropout_p, seqlens=seqlens,
+                               segments=segments)
 
 
 # ---------------------------------------------------------------- K14 / K15

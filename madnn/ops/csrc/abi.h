@@ -185,6 +185,10 @@ int madnn_attn_dropout_threshold(double p);
 hipError_t madnn_attn_dropout_mask(uint8_t* out, int B, int H, int S, uint32_t threshold, uint64_t seed,
                                    uint64_t offset, hipStream_t st);
 hipError_t madnn_attn_bwd(const MadnnAttnArgs* a, int D, int causal, hipStream_t st);
+// MadnnAttnArgs::seg of a batch of packed rows: ids int32 [B, S] (a document = a maximal run of equal
+// consecutive ids), bounds int32 [B, 2, S] = (first token of the token's document, one past its last).
+// One launch, one workgroup per row, any S.
+hipError_t madnn_attn_segment_bounds(const int32_t* ids, int32_t* bounds, int B, int S, hipStream_t st);
 
 // ---- conv.hip ----
 // key 0: forward/dgrad grid target, 1: weight-grad workgroups, 2: XCD remap (0/1), 3: ring main loop (0/1),

@@ -44,6 +44,11 @@ struct MadnnAttnArgs {
   // clamp(seqlens[b], 0, S) valid tokens followed by padding; null = every position valid (the dense
   // kernels).  Last field: the offsets above are those of the struct without it.
   const int32_t* seqlens;
+  // packed documents (attn.hip header, "Packed documents"): int32 [B, 2, S], seg[b][0][s] = the first
+  // token of token s's document, seg[b][1][s] = one past its last (madnn_attn_segment_bounds); the
+  // kernels clamp what they read (lo into [0, s], hi into [s + 1, S]).  null = no segments.  Not with
+  // seqlens, not with dropout.  Last field: the offsets above are those of the struct without it.
+  const int32_t* seg;
 };
 
 }

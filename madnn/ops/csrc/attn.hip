@@ -67,6 +67,36 @@
 //  * a workgroup whose 128 rows all lie at or past L writes those zeros (and its zero cpart row: the
 //    finalize sums every row) and returns before any tile work;
 //  * the dropout mask stays the same function of the absolute (b, h, q, k).
+//
+// Packed documents (the SEG instantiations of the three register-staged kernels; never the ring kernels,
+// never with VARLEN or DROP).  a.seg is int32 [B, 2, S]: token s of row b belongs to the document
+// [lo, hi) = [seg[b][0][s], seg[b][1][s]) and query q attends to the keys lo_q <= k < hi_q (and k <= q
+// when causal).  The mask is symmetric -- k lies in q's document iff q lies in k's -- so the same pair
+// of bounds serves the kernels with the query on the lane and dK/dV with the key on the lane.  What is
+// read is clamped, lo into [0, s] and hi into [s + 1, S]: a malformed tensor gives wrong values, never
+// an out-of-range tile or address, and every row sees at least itself (l > 0, a finite LSE).
+//  * tile range of a workgroup (wave-uniform, SGPRs): the bounds do not decrease along a row, so the
+//    first row's lo and the last row's hi (last row < S) bound the block: forward / dQ over query rows
+//    [r0, r0 + 128) walk the key tiles lo[r0] / 64 .. ceil(hi[last] / 64) (causal: up to min(S, r0 +
+//    128)); dK/dV over key rows [r0, r0 + 128) walks the query tiles lo[r0] / 64 (causal: r0 / 64) ..
+//    ceil(hi[last] / 64).  The loops start at that tile and number their LDS buffers from their own
+//    trip count;
+//  * a wave computes a tile only if it meets [lo of its first row, hi of its last row) (else it only
+//    stages, like a causal wave past its diagonal);
+//  * per lane the one limit becomes two: offset kb*32 + acc_row(r, 0) is kept iff it lies in
+//    [lo - k0 - 4hh, hi' - 1 - k0 - 4hh], hi' = min(hi, row + 1) when causal (dK/dV: the offsets are
+//    queries, k0 the tile's first query, and the causal lower limit is the key row itself, as lo <= row).
+//    The mask block is skipped for a tile inside every row's interval: first key >= lo of the wave's
+//    LAST row, last key < hi of its FIRST row.  Forward / dQ, causal: the diagonal is folded into the wave's
+//    upper bounds once (SegWave), so "meets" and "inside" are a causal kernel's only tile tests as well;
+//  * the forward's running reference must not move before a row has seen a valid key.  A row whose
+//    keys in a computed tile are all masked has top = -inf, but the wave-wide __any takes the rescale
+//    branch for its neighbours: moving m = mi to kNegBig there would start the row's next accumulators
+//    at -1e30, which absorbs the scores (every p = 1).  Causal rows always see key 0 in their first
+//    tile and VARLEN's dead rows are overwritten, so only SEG meets it -- a document boundary inside a
+//    wave on the first tile it computes -- and softmax_tile<SEG> leaves such a row's m, mi and
+//    reference register alone;
+//  * lse / delta / cpart layouts and the grid are the dense ones; the column sums cover every row.
 #include <type_traits>
 
 #include "abi.h"
@@ -177,6 +207,56 @@ __device__ __forceinline__ int seq_len(const int32_t* seqlens, int b, int S) {
   }
 }
 
+// SEG: the clamped document bounds of token `row` (0 <= row < S) of sequence b, seg = [B][2][S]
+__device__ __forceinline__ int seg_lo(const int32_t* seg, int b, int S, int row) {
+  return min(max(seg[(int64_t)b * 2 * S + row], 0), row);
+}
+__device__ __forceinline__ int seg_hi(const int32_t* seg, int b, int S, int row) {
+  return min(max(seg[((int64_t)b * 2 + 1) * S + row], row + 1), S);
+}
+
+// SEG: what one wave needs of the bounds.  Wave-uniform (SGPRs; `w0` = the wave's first row, itself
+// wave-uniform): lo / hi of its first and of its last row below S.  Per lane: the row's own first and
+// last visible index, [lo, last] = [lo, hi - 1].  With `upto_row` (causal queries) the diagonal is folded into
+// the upper bounds -- last = min(hi - 1, row), hi_first = min(hi_first, w0 + 1), hi_last = min(hi_last, w0 + 32)
+// -- so meets() and inside() are the only tile tests of a causal kernel too (the separate diagonal tests gave
+// the causal D = 128 kernels another schedule, which spilled under the 2-wave bound).
+struct SegWave {
+  int lo_first, lo_last, hi_first, hi_last;
+  int lo, last;
+  __device__ __forceinline__ void init(const int32_t* seg, int b, int S, int w0, int row, bool upto_row) {
+    const int f = min(w0, S - 1), l = min(w0 + 31, S - 1), rc = min(row, S - 1);
+    lo_first = __builtin_amdgcn_readfirstlane(seg_lo(seg, b, S, f));
+    lo_last = __builtin_amdgcn_readfirstlane(seg_lo(seg, b, S, l));
+    hi_first = __builtin_amdgcn_readfirstlane(seg_hi(seg, b, S, f));
+    hi_last = __builtin_amdgcn_readfirstlane(seg_hi(seg, b, S, l));
+    lo = seg_lo(seg, b, S, rc);
+    last = seg_hi(seg, b, S, rc) - 1;
+    if (upto_row) {
+      last = min(last, row);
+      hi_first = min(hi_first, w0 + 1);
+      hi_last = min(hi_last, w0 + 32);
+    }
+  }
+  // does the 64-row tile at x0 meet the wave's rows' intervals at all / lie inside every one of them
+  __device__ __forceinline__ bool meets(int x0) const { return x0 + kTile > lo_first && x0 < hi_last; }
+  __device__ __forceinline__ bool inside(int x0) const { return x0 >= lo_last && x0 + kTile <= hi_first; }
+};
+
+// SEG: offset `off` (a compile-time constant) is kept iff lim_lo <= off <= lim_hi: two compares into scalar
+// masks and one select per element (one subtract and one unsigned compare instead held 16 temporaries live
+// and spilled at D = 128)
+__device__ __forceinline__ bool seg_keep(int off, int lim_lo, int lim_hi) { return (off >= lim_lo) & (off <= lim_hi); }
+
+// SEG: one of a tile's two limits: bound `bound` as an offset into the tile at x0, for lane half hh
+__device__ __forceinline__ int seg_lim(int bound, int x0, int hh) { return bound - x0 - 4 * hh; }
+
+// SEG: first and one-past-last 64-row tile of the workgroup whose 128 rows start at r0 (wave-uniform)
+__device__ __forceinline__ void seg_block(const int32_t* seg, int b, int S, int r0, int& lo, int& hi) {
+  lo = __builtin_amdgcn_readfirstlane(seg_lo(seg, b, S, r0));
+  hi = __builtin_amdgcn_readfirstlane(seg_hi(seg, b, S, min(r0 + kRowsWG, S) - 1));
+}
+
 // One [D] row of zeros at row `row` of a [.., heads, D] output (a padded position)
 template <int D>
 __device__ __forceinline__ void store_zero_row(uint16_t* rowp, int hh) {
@@ -245,7 +325,9 @@ constexpr float kRescaleSlack = 8.f;
 // is mi - min(acc); when it passes m + slack (always on the first tile) O and l are rescaled, the
 // tile's acc shifted to the new reference and the splatted reference tuple (the next tiles' initial
 // accumulator) updated.  Then acc <- p = exp2(-acc) and l += the lane's part of the row sums.
-template <int DB>
+// SEG: a row with every key of the tile masked (mn = +inf) keeps m, mi and its reference register
+// (header, "Packed documents": the reference must not move before the row has seen a valid key).
+template <int DB, bool SEG = false>
 __device__ __forceinline__ void softmax_tile(f32x16 (&sc)[2], f32x16 (&o)[DB], float& m, float& mi, float& l,
                                              f32x16& mref) {
   float mn = sc[0][0];
@@ -257,7 +339,8 @@ __device__ __forceinline__ void softmax_tile(f32x16 (&sc)[2], f32x16 (&o)[DB], f
   mn = fminf(mn, __shfl_xor(mn, 32));
   const float top = mi - mn;
   if (__any(top > m + kRescaleSlack)) {
-    const float mnew = fmaxf(m, top);
+    const bool seen = !SEG || mn < __builtin_inff();
+    const float mnew = seen ? fmaxf(m, top) : m;
     const float alpha = ex2(m - mnew);
     l *= alpha;
 #pragma unroll
@@ -265,14 +348,15 @@ __device__ __forceinline__ void softmax_tile(f32x16 (&sc)[2], f32x16 (&o)[DB], f
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
     }
-    const float adj = mnew - mi;
+    const float adj = seen ? mnew - mi : 0.f;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) sc[kb][r] += adj;
     }
-    m = mi = mnew;
-    mref = splat16(mnew);
+    m = mnew;
+    mi = seen ? mnew : mi;
+    mref = splat16(mi);
   }
   float rs = 0.f;
 #pragma unroll
@@ -289,15 +373,17 @@ __device__ __forceinline__ void softmax_tile(f32x16 (&sc)[2], f32x16 (&o)[DB], f
 
 // D = 128 is built for 2 waves per SIMD (256 VGPRs, a few spills; 348 and one wave unbounded):
 // +27 % at Llama-3 8B's shape, profiles/r5_attn_ab_occupancy.json
-template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false, bool SEG = false>
 __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(const MadnnAttnArgs a) {
+  static_assert(!SEG || (!DROP && !VARLEN), "SEG excludes DROP and VARLEN");
   constexpr int DS = D / 16, DB = D / 32;
-  // VARLEN at D = 128: ONE staging tuple, the next K tile held during the scores, the next V tile during
+  // VARLEN / SEG at D = 128: ONE staging tuple, the next K tile held during the scores, the next V tile during
   // the P.V products (16 VGPRs fewer than K and V together: no spills under the 2-wave bound)
-  constexpr bool ONESTAGE = VARLEN && D == 128;
+  constexpr bool ONESTAGE = (VARLEN || SEG) && D == 128;
   __shared__ __attribute__((aligned(16))) uint16_t sK[2][kTile * D];
   __shared__ __attribute__((aligned(16))) uint16_t sV[2][kTile * D];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
+  const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
+  const int wave = SEG ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;  // SEG: its tile tests are scalar
   const int nqb = (a.S + kRowsWG - 1) / kRowsWG;
   int qblk, b, h;
   map_block(nqb, a.H, CAUSAL, qblk, b, h);
@@ -333,33 +419,43 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
   for (int d = 0; d < DB; ++d) o[d] = zero16();
   float m = kNegBig, mi = 0.f, l = 0.f;
   f32x16 mref = zero16();
-  const int kv_end = CAUSAL ? min(L, qblk * kRowsWG + kRowsWG) : L;
+  int kv_end = CAUSAL ? min(L, qblk * kRowsWG + kRowsWG) : L;
+  int t_beg = 0;  // SEG: the key tile that holds the block's first row's lo
+  SegWave sg;
+  if constexpr (SEG) {
+    int blo, bhi;
+    seg_block(a.seg, b, a.S, qblk * kRowsWG, blo, bhi);
+    if (!CAUSAL) kv_end = bhi;
+    t_beg = blo / kTile;
+    sg.init(a.seg, b, a.S, q0w, qrow, CAUSAL);
+  }
   const int ntiles = (kv_end + kTile - 1) / kTile;
 
   // global loads (see TileStage); ONESTAGE: stk alone, K then V, through buffer loads bounded at row L (no
   // per-lane 64-bit addresses, branches or zero fills: with them the full-attention kernel still spilled)
   TileStage<D, ONESTAGE> stk, stv;
-  stk.load(kb_, a.k_ss, 0, L, tid);
+  stk.load(kb_, a.k_ss, t_beg * kTile, L, tid);
   if constexpr (ONESTAGE) {
     stk.store(sK[0], tid);
-    stk.load(vb_, a.v_ss, 0, L, tid);
+    stk.load(vb_, a.v_ss, t_beg * kTile, L, tid);
     stk.store(sV[0], tid);
   } else {
-    stv.load(vb_, a.v_ss, 0, L, tid);
+    stv.load(vb_, a.v_ss, t_beg * kTile, L, tid);
     stk.store(sK[0], tid);
     stv.store(sV[0], tid);
   }
   __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
-    const int cur = t & 1;
+  for (int t = t_beg; t < ntiles; ++t) {
+    const int cur = (t - t_beg) & 1;  // buffers are numbered from the loop's own counter
     const bool more = t + 1 < ntiles;
     if (more) {
       stk.load(kb_, a.k_ss, (t + 1) * kTile, L, tid);
       if constexpr (!ONESTAGE) stv.load(vb_, a.v_ss, (t + 1) * kTile, L, tid);
     }
     const int k0 = t * kTile;
-    // VARLEN: a wave whose 32 rows are all padding only stages tiles
-    if ((!CAUSAL || k0 <= q0w + 31) && (!VARLEN || q0w < L)) {
+    // VARLEN: a wave whose 32 rows are all padding only stages tiles; SEG: so does a wave none of whose
+    // rows' documents meets the tile (sg holds the diagonal when causal)
+    if (SEG ? sg.meets(k0) : (!CAUSAL || k0 <= q0w + 31) && (!VARLEN || q0w < L)) {
       f32x16 sc[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
@@ -367,7 +463,18 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
 #pragma unroll
         for (int s = 0; s < DS; ++s) sc[kb] = mfma(lds_row<D>(sK[cur], kb * 32 + l32, 2 * s + hh), qf[s], sc[kb]);
       }
-      if ((k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w)) {
+      if constexpr (SEG) {
+        if (!sg.inside(k0)) {
+          // the same compile-time offset against the row's two limits (header, "Packed documents")
+          const int lim_lo = seg_lim(sg.lo, k0, hh), lim_hi = seg_lim(sg.last, k0, hh);
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              sc[kb][r] = seg_keep(kb * 32 + acc_row(r, 0), lim_lo, lim_hi) ? sc[kb][r] : __builtin_inff();
+          }
+        }
+      } else if ((k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w)) {
         // key k0 + kb*32 + acc_row(r, hh) is valid iff its compile-time offset kb*32 + acc_row(r, 0)
         // <= lim (one compare + select per element)
         const int lim = (CAUSAL ? min(L - 1, qrow) : L - 1) - k0 - 4 * hh;
@@ -377,7 +484,7 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
           for (int r = 0; r < 16; ++r) sc[kb][r] = kb * 32 + acc_row(r, 0) <= lim ? sc[kb][r] : __builtin_inff();
         }
       }
-      softmax_tile<DB>(sc, o, m, mi, l, mref);
+      softmax_tile<DB, SEG>(sc, o, m, mi, l, mref);
       if constexpr (DROP) {  // l has the undropped row sum; O takes M . P (rp is folded into inv)
         const DropRng rng = drop_rng(a.drop_seed, a.drop_offset);
 #pragma unroll
@@ -457,20 +564,21 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_fwd_kernel(co
 // at D = 64 the 2-wave build measured neutral).
 // DROP: dS = P (rp M dPraw - delta): the mask and rp go onto the raw dP before the subtraction, so the
 // dP accumulators start at zero at D = 64 too (no ACCD).
-template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false, bool SEG = false>
 __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel(const MadnnAttnArgs a) {
+  static_assert(!SEG || (!DROP && !VARLEN), "SEG excludes DROP and VARLEN");
   constexpr int DS = D / 16, DB = D / 32;
   constexpr bool ACCD = D == 64 && !DROP, KSPLIT = D == 128;
-  // VARLEN at D = 128: ONE staging tuple, the next K tile held during the first 32-key half, the next V
+  // VARLEN / SEG at D = 128: ONE staging tuple, the next K tile held during the first 32-key half, the next V
   // tile during the second (16 VGPRs fewer than K and V together: no spills under the 2-wave bound)
-  constexpr bool ONESTAGE = VARLEN && D == 128;
+  constexpr bool ONESTAGE = (VARLEN || SEG) && D == 128;
   // K and V stages in one block: after the loop the column-sum epilogue reuses all of it as a
   // [128 rows][D] fp32 image (4 * 64 * D bf16 = 128 * D fp32)
   __shared__ __attribute__((aligned(16))) uint16_t sKV[4][kTile * D];
   uint16_t(*sK)[kTile * D] = sKV;
   uint16_t(*sV)[kTile * D] = sKV + 2;
   const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, hh = lane >> 5;
-  const int wave = VARLEN ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+  const int wave = VARLEN || SEG ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int nqb = (a.S + kRowsWG - 1) / kRowsWG;
   int qblk, b, h;
   map_block(nqb, a.H, CAUSAL, qblk, b, h);
@@ -533,21 +641,28 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
   f32x16 ndl;
 #pragma unroll
   for (int r = 0; r < 16; ++r) ndl[r] = -dl;
-  const int kv_end = CAUSAL ? min(L, qblk * kRowsWG + kRowsWG) : L;
+  int blo = 0, bhi = 0;  // SEG: the block's first row's lo, its last row's hi
+  SegWave sg;
+  if constexpr (SEG) {
+    seg_block(a.seg, b, a.S, qblk * kRowsWG, blo, bhi);
+    sg.init(a.seg, b, a.S, q0w, qrow, CAUSAL);
+  }
+  const int kv_end = CAUSAL ? min(L, qblk * kRowsWG + kRowsWG) : SEG ? bhi : L;
   const int ntiles = (kv_end + kTile - 1) / kTile;
+  const int t_beg = SEG ? blo / kTile : 0;  // SEG: the loop starts at the key tile that holds blo
   TileStage<D, true> stk, stv;  // ONESTAGE: stk alone, K then V
-  stk.load(kb_, a.k_ss, 0, L, tid);
+  stk.load(kb_, a.k_ss, t_beg * kTile, L, tid);
   if constexpr (ONESTAGE) {
     stk.store(sK[0], tid);
-    stk.load(vb_, a.v_ss, 0, L, tid);
+    stk.load(vb_, a.v_ss, t_beg * kTile, L, tid);
     stk.store(sV[0], tid);
   } else {
-    stv.load(vb_, a.v_ss, 0, L, tid);
+    stv.load(vb_, a.v_ss, t_beg * kTile, L, tid);
     stk.store(sK[0], tid);
     stv.store(sV[0], tid);
   }
   __syncthreads();
-  int t = 0;
+  int t = t_beg;
   auto tile = [&](auto curc) {
     constexpr int cur = decltype(curc)::value;
     const bool more = t + 1 < ntiles;
@@ -566,11 +681,14 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
     };
     const int k0 = t * kTile;
     // VARLEN: a wave whose 32 rows are all padding only stages tiles
-    const bool live = (!CAUSAL || k0 <= q0w + 31) && (!VARLEN || q0w < L);
+    // SEG: nor does a wave none of whose rows' documents meets the tile (sg holds the diagonal when causal)
+    const bool live = SEG ? sg.meets(k0) : (!CAUSAL || k0 <= q0w + 31) && (!VARLEN || q0w < L);
     if (KSPLIT && live) {
       // one 32-key half at a time: S, dP, dS and its dQ products, so only one half's accumulators live
-      const bool edge = (k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w);
-      const int lim = (CAUSAL ? min(qrow, L - 1) : L - 1) - k0 - 4 * hh;
+      // (SEG: the mask block is entered unless the tile lies inside every row's interval)
+      const bool edge = SEG ? !sg.inside(k0) : (k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w);
+      int lim = (CAUSAL ? min(qrow, L - 1) : L - 1) - k0 - 4 * hh, lim_hi = 0;
+      if constexpr (SEG) lim = seg_lim(sg.lo, k0, hh), lim_hi = seg_lim(sg.last, k0, hh);  // lim <= offset <= lim_hi
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         f32x16 sc = zero16(), dp = zero16();
@@ -581,7 +699,10 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
         }
         if (edge) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) sc[r] = (kb * 32 + acc_row(r, 0) <= lim) ? sc[r] : __builtin_inff();
+          for (int r = 0; r < 16; ++r) {
+            const int off = kb * 32 + acc_row(r, 0);
+            sc[r] = (SEG ? seg_keep(off, lim, lim_hi) : off <= lim) ? sc[r] : __builtin_inff();
+          }
         }
         if constexpr (DROP) {
           drop_bytes_q(drop_rng(a.drop_seed, a.drop_offset), b * a.H + h, qrow, k0 + kb * 32, hh, lane,
@@ -611,14 +732,18 @@ __global__ __launch_bounds__(kThreads, D == 128 ? 2 : 1) void attn_bwd_dq_kernel
       }
       // masking as one wave-uniform block on the scores (exp2(-inf) = 0): interior tiles run
       // none of it (a per-element `if` costs an exec-mask branch per element)
-      if ((k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w)) {
+      if (SEG ? !sg.inside(k0) : (k0 + kTile > L) || (CAUSAL && k0 + kTile - 1 > q0w)) {
         // key = k0 + off + 4 hh with off = kb*32 + acc_row(r, 0) a compile-time constant: the mask is
-        // one compare of that constant against a per-lane limit (acc = +inf: p = 0)
-        const int lim = (CAUSAL ? min(qrow, L - 1) : L - 1) - k0 - 4 * hh;
+        // one compare of that constant against a per-lane limit (acc = +inf: p = 0); SEG: two limits
+        int lim = (CAUSAL ? min(qrow, L - 1) : L - 1) - k0 - 4 * hh, lim_hi = 0;
+        if constexpr (SEG) lim = seg_lim(sg.lo, k0, hh), lim_hi = seg_lim(sg.last, k0, hh);
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) sc[kb][r] = (kb * 32 + acc_row(r, 0) <= lim) ? sc[kb][r] : __builtin_inff();
+          for (int r = 0; r < 16; ++r) {
+            const int off = kb * 32 + acc_row(r, 0);
+            sc[kb][r] = (SEG ? seg_keep(off, lim, lim_hi) : off <= lim) ? sc[kb][r] : __builtin_inff();
+          }
         }
       }
       if constexpr (DROP) {
@@ -1095,8 +1220,9 @@ __global__ __launch_bounds__(kThreads) void attn_fwd_dma_kernel(const MadnnAttnA
 // same dS = P (rp M dPraw - delta) as dQ (no ACCD).  At D = 64 it is bounded to 2 waves per SIMD (256 VGPRs,
 // no spill; 264 and one wave unbounded): forward + backward -16 % / -13 % at the GPT-2 medium / BERT-large
 // shapes (docs/PERF.md, round 11).
-template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false, bool SEG = false>
 __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dkdv_kernel(const MadnnAttnArgs a) {
+  static_assert(!SEG || (!DROP && !VARLEN), "SEG excludes DROP and VARLEN");
   constexpr int DS = D / 16, DB = D / 32;
   constexpr bool ACCD = D == 64 && !DROP;
   // VARLEN with dropout at D = 64: ONE staging tuple, the next Q tile held during the S / dP products,
@@ -1159,8 +1285,19 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
     dk[d] = zero16();
     dv[d] = zero16();
   }
-  const int t0 = CAUSAL ? (kblk * kRowsWG) / kTile : 0;
-  const int nt = (L + kTile - 1) / kTile - t0;  // query tiles with a valid row
+  int blo = 0, bhi = 0;  // SEG: the block's first key's lo, its last key's hi
+  SegWave sg;
+  if constexpr (SEG) {
+    seg_block(a.seg, b, a.S, kblk * kRowsWG, blo, bhi);
+    sg.init(a.seg, b, a.S, kblk * kRowsWG + __builtin_amdgcn_readfirstlane(wave) * 32, krow, false);
+  }
+  // SEG: the query tiles from the first key's lo (causal: lo <= the key row, so from the diagonal as ever) to
+  // the end of the last key's document
+  const int t0 = CAUSAL ? (kblk * kRowsWG) / kTile : SEG ? blo / kTile : 0;
+  // SEG: the first query this lane's key is visible to (causal: the key row itself, as lo <= row); the last is
+  // sg.last.  Query offset `off` of a tile at q0 is kept iff seg_from - q0 - 4hh <= off <= sg.last - q0 - 4hh
+  const int seg_from = SEG ? (CAUSAL ? krow : sg.lo) : 0;
+  const int nt = ((SEG ? bhi : L) + kTile - 1) / kTile - t0;  // query tiles with a valid row
   const int total = G * nt;
   // tile `it` = (query head hk*G + it / nt, query tile t0 + it % nt); the loop walks it with two
   // counters instead of a per-tile integer division
@@ -1248,7 +1385,10 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
     cur_t = nxt_t;
     const int hq = hk * G + cur_h;
     cur_h = nxt_h;
-    if (!CAUSAL || q0 + kTile - 1 >= k0w) {
+    // SEG: a wave none of whose keys' documents meets the query tile only stages
+    bool live = !CAUSAL || q0 + kTile - 1 >= k0w;
+    if constexpr (SEG) live = live && sg.meets(q0);
+    if (live) {
       f32x16 sc[2], dp[2];
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb) {
@@ -1268,7 +1408,17 @@ __global__ __launch_bounds__(kThreads, DROP && D == 64 ? 2 : 1) void attn_bwd_dk
       if constexpr (ONESTAGE) {  // after the S / dP products: next Q -> LDS, next dO -> registers
         if (more) q_out_do_in();
       }
-      if (CAUSAL && q0 < k0w + 31) {  // diagonal tile: one wave-uniform masking block
+      if constexpr (SEG) {  // unless the tile lies inside every key's interval (and past the diagonal)
+        if (!sg.inside(q0) || (CAUSAL && q0 < k0w + 31)) {
+          const int lim_lo = seg_lim(seg_from, q0, hh), lim_hi = seg_lim(sg.last, q0, hh);
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              sc[qb][r] = seg_keep(qb * 32 + acc_row(r, 0), lim_lo, lim_hi) ? sc[qb][r] : -__builtin_inff();
+          }
+        }
+      } else if (CAUSAL && q0 < k0w + 31) {  // diagonal tile: one wave-uniform masking block
         const int lo = krow - q0 - 4 * hh;  // query offset qb*32 + acc_row(r, 0) must reach it
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
@@ -1415,6 +1565,54 @@ __global__ __launch_bounds__(256) void attn_dropout_mask_kernel(uint8_t* __restr
   out[idx] = drop_byte(word, k & 3) < threshold ? 1 : 0;
 }
 
+// Document bounds of packed rows (MadnnAttnArgs::seg) from the ids: one workgroup per row.  A token
+// starts a document iff it is the row's first or its id differs from its left neighbour's; lo[s] is the
+// last start at or before s (an inclusive forward max-scan of start ? s : -1), hi[s] the first start after
+// s, S if there is none (an inclusive backward min-scan of the right neighbour's start ? s + 1 : S).  Both
+// scans run over 256-token chunks in LDS (Hillis-Steele, double-buffered) with the running value carried
+// from chunk to chunk, so any S works.
+constexpr int kSegChunk = 256;
+__global__ __launch_bounds__(kSegChunk) void attn_segment_bounds_kernel(const int32_t* __restrict__ ids,
+                                                                        int32_t* __restrict__ bounds, int S) {
+  __shared__ int sc[2][kSegChunk];
+  const int tid = threadIdx.x;
+  const int32_t* row = ids + (int64_t)blockIdx.x * S;
+  int32_t* lo = bounds + (int64_t)blockIdx.x * 2 * S;
+  int32_t* hi = lo + S;
+  int carry = 0;
+  for (int c0 = 0; c0 < S; c0 += kSegChunk) {
+    const int s = c0 + tid;
+    sc[0][tid] = s < S && (s == 0 || row[s] != row[s - 1]) ? s : -1;
+    __syncthreads();
+    int buf = 0;
+    for (int d = 1; d < kSegChunk; d <<= 1, buf ^= 1) {
+      int x = sc[buf][tid];
+      if (tid >= d) x = max(x, sc[buf][tid - d]);
+      sc[buf ^ 1][tid] = x;
+      __syncthreads();
+    }
+    if (s < S) lo[s] = max(carry, sc[buf][tid]);
+    carry = max(carry, sc[buf][kSegChunk - 1]);
+    __syncthreads();  // the next chunk overwrites sc[0]
+  }
+  carry = S;
+  for (int c0 = (S - 1) / kSegChunk * kSegChunk; c0 >= 0; c0 -= kSegChunk) {
+    const int s = c0 + tid;
+    sc[0][tid] = s + 1 < S && row[s + 1] != row[s] ? s + 1 : S;
+    __syncthreads();
+    int buf = 0;
+    for (int d = 1; d < kSegChunk; d <<= 1, buf ^= 1) {
+      int x = sc[buf][tid];
+      if (tid + d < kSegChunk) x = min(x, sc[buf][tid + d]);
+      sc[buf ^ 1][tid] = x;
+      __syncthreads();
+    }
+    if (s < S) hi[s] = min(carry, sc[buf][tid]);
+    carry = min(carry, sc[buf][0]);
+    __syncthreads();
+  }
+}
+
 // madnn_attn_tune keys (A/B and the tests of the register-staged fallbacks, which serve sequence
 // lengths that are not multiples of 64 and D = 128): 7 = D = 64 dK/dV on the 3-stage LDS-DMA ring,
 // 8 = D = 64 forward on the K / V LDS-DMA ring (0: the register-staged kernels)
@@ -1424,7 +1622,10 @@ static int g_attn_fwd_dma = 1;
 template <int D, bool CAUSAL>
 hipError_t launch_fwd(const MadnnAttnArgs& a, hipStream_t st) {
   const int nqb = (a.S + kRowsWG - 1) / kRowsWG;
-  if (a.seqlens != nullptr) {  // per-sequence lengths: the register-staged kernel at every shape, as dropout
+  if (a.seg != nullptr) {  // packed documents: the register-staged SEG kernel at every shape (no seqlens, no dropout)
+    if (a.seqlens != nullptr || a.drop_threshold != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, false, false, true>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
+  } else if (a.seqlens != nullptr) {  // per-sequence lengths: the register-staged kernel at every shape, as dropout
     if (a.drop_threshold != 0) {
       hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, true, true>), dim3(nqb * a.B * a.H), dim3(kThreads), 0, st, a);
     } else {
@@ -1443,6 +1644,13 @@ hipError_t launch_fwd(const MadnnAttnArgs& a, hipStream_t st) {
 template <int D, bool CAUSAL>
 hipError_t launch_bwd(const MadnnAttnArgs& a, hipStream_t st) {
   const int nb = (a.S + kRowsWG - 1) / kRowsWG;
+  if (a.seg != nullptr) {  // packed documents: never the ring kernel
+    if (a.seqlens != nullptr || a.drop_threshold != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CAUSAL, false, false, true>), dim3(nb * a.B * a.H), dim3(kThreads), 0, st, a);
+    MADNN_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, false, false, true>), dim3(nb * a.B * a.Hkv), dim3(kThreads), 0, st, a);
+    return hipGetLastError();
+  }
   if (a.seqlens != nullptr) {  // per-sequence lengths: never the ring kernel
     if (a.drop_threshold != 0) {
       hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CAUSAL, true, true>), dim3(nb * a.B * a.H), dim3(kThreads), 0, st, a);
@@ -1518,6 +1726,12 @@ hipError_t madnn_attn_dropout_mask(uint8_t* out, int B, int H, int S, uint32_t t
   if ((n + 255) / 256 > 0x7fffffff) return hipErrorInvalidValue;
   hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, S, n, threshold,
                      seed, offset);
+  return hipGetLastError();
+}
+
+hipError_t madnn_attn_segment_bounds(const int32_t* ids, int32_t* bounds, int B, int S, hipStream_t st) {
+  if (B <= 0 || S <= 0) return hipSuccess;
+  hipLaunchKernelGGL(attn_segment_bounds_kernel, dim3(B), dim3(kSegChunk), 0, st, ids, bounds, S);
   return hipGetLastError();
 }
 

@@ -1376,7 +1376,8 @@ void attn_check(const at::Tensor& t, const char* name, int64_t D) {
 }
 
 MadnnAttnArgs attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
-                        const c10::optional<at::Tensor>& seqlens = c10::nullopt) {
+                        const c10::optional<at::Tensor>& seqlens = c10::nullopt,
+                        const c10::optional<at::Tensor>& segments = c10::nullopt) {
   const int64_t D = q.size(3);
   TORCH_CHECK(madnn_attn_supported((int)D), "attention: head dim must be 64 or 128");
   attn_check(q, "q", D);
@@ -1406,6 +1407,16 @@ MadnnAttnArgs attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tens
                 "attention: seqlens must be a contiguous int32 [B] tensor on the inputs' device");
     a.seqlens = seqlens->data_ptr<int32_t>();
   }
+  // document bounds of packed rows (null: none), the result of segment_bounds.  Shape, dtype and place are
+  // checked here; the values are clamped by the kernels (lo into [0, s], hi into [s + 1, S]): no host sync.
+  if (segments.has_value() && segments->defined()) {
+    TORCH_CHECK(segments->scalar_type() == at::kInt && segments->dim() == 3 && segments->size(0) == q.size(0) &&
+                    segments->size(1) == 2 && segments->size(2) == q.size(1) && segments->is_contiguous() &&
+                    segments->device() == q.device(),
+                "attention: segments must be a contiguous int32 [B, 2, S] tensor (segment_bounds) on the inputs' device");
+    TORCH_CHECK(a.seqlens == nullptr, "attention: segments and seqlens exclude each other");
+    a.seg = segments->data_ptr<int32_t>();
+  }
   return a;
 }
 
@@ -1419,6 +1430,7 @@ uint32_t attn_drop_threshold(double p) {
 
 void attn_set_dropout(MadnnAttnArgs& a, double p, int64_t seed, int64_t offset) {
   if (p == 0.0) return;  // drop_threshold = 0: the kernels without dropout
+  TORCH_CHECK(a.seg == nullptr, "attention: segments with dropout p > 0 have no kernel");
   a.drop_threshold = attn_drop_threshold(p);
   a.drop_rp = 256.f / (float)a.drop_threshold;
   a.drop_seed = (uint64_t)seed;
@@ -1427,8 +1439,9 @@ void attn_set_dropout(MadnnAttnArgs& a, double p, int64_t seed, int64_t offset) 
 
 std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                             bool causal, double scale, double p, int64_t seed, int64_t offset,
-                                            const c10::optional<at::Tensor>& seqlens) {
-  MadnnAttnArgs a = attn_args(q, k, v, scale, seqlens);
+                                            const c10::optional<at::Tensor>& seqlens,
+                                            const c10::optional<at::Tensor>& segments) {
+  MadnnAttnArgs a = attn_args(q, k, v, scale, seqlens, segments);
   attn_set_dropout(a, p, seed, offset);
   at::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor o = at::empty({q.size(0), q.size(1), q.size(2), q.size(3)}, q.options());
@@ -1444,8 +1457,9 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tenso
 void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
               const at::Tensor& o, const at::Tensor& lse, const at::Tensor& dq, const at::Tensor& dk,
               const at::Tensor& dv, bool causal, double scale, const c10::optional<at::Tensor>& colsum, double p,
-              int64_t seed, int64_t offset, const c10::optional<at::Tensor>& seqlens) {
-  MadnnAttnArgs a = attn_args(q, k, v, scale, seqlens);
+              int64_t seed, int64_t offset, const c10::optional<at::Tensor>& seqlens,
+              const c10::optional<at::Tensor>& segments) {
+  MadnnAttnArgs a = attn_args(q, k, v, scale, seqlens, segments);
   attn_set_dropout(a, p, seed, offset);
   const int64_t D = q.size(3);
   TORCH_CHECK(o.is_contiguous() && o.sizes() == q.sizes(), "attn_bwd: o must be contiguous [B, S, H, D]");
@@ -1487,6 +1501,21 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
     check(madnn_attn_colsum_finalize(a.cpart, R, C, colsum->data_ptr(), colsum->scalar_type() == at::kBFloat16 ? 1 : 0,
                                      cur_stream(q)),
           "attn_colsum");
+}
+
+// Document bounds of packed rows: ids integer [B, S] on the device -> int32 [B, 2, S] (lo, hi), one launch.
+// Ids of another integer dtype are converted to int32 first (documents are runs of equal int32 values).
+at::Tensor segment_bounds(const at::Tensor& ids) {
+  check_dev(ids, "ids");
+  TORCH_CHECK(ids.dim() == 2 && at::isIntegralType(ids.scalar_type(), false), "segment_bounds: ids must be an integer [B, S]");
+  TORCH_CHECK(ids.size(0) < (1ll << 30) && ids.size(1) < (1ll << 30), "segment_bounds: problem too large");
+  at::hip::HIPGuardMasqueradingAsCUDA guard(ids.device());
+  const at::Tensor idc = ids.to(at::kInt).contiguous();
+  at::Tensor out = at::empty({ids.size(0), 2, ids.size(1)}, idc.options());
+  check(madnn_attn_segment_bounds(idc.data_ptr<int32_t>(), out.data_ptr<int32_t>(), (int)ids.size(0), (int)ids.size(1),
+                                  cur_stream(ids)),
+        "segment_bounds");
+  return out;
 }
 
 // The K8 dropout mask as a tensor: uint8 [B, H, S, S], 1 = kept (tests / debugging; the attention
@@ -1680,12 +1709,13 @@ TORCH_LIBRARY(madnn, m) {
       "Tensor? w_r, Tensor save_mean_r, Tensor save_invstd_r) -> Tensor[]");
   m.def(
       "attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, float scale, float p=0.0, int seed=0, int offset=0, "
-      "Tensor? seqlens=None) -> "
+      "Tensor? seqlens=None, Tensor? segments=None) -> "
       "(Tensor, Tensor)");
   m.def(
       "attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, "
       "Tensor(c!) dv, bool causal, float scale, Tensor(d!)? colsum=None, float p=0.0, int seed=0, int offset=0, "
-      "Tensor? seqlens=None) -> ()");
+      "Tensor? seqlens=None, Tensor? segments=None) -> ()");
+  m.def("segment_bounds(Tensor ids) -> Tensor");
   m.def("attn_dropout_mask(int B, int H, int S, float p, int seed, int offset) -> Tensor", &attn_dropout_mask);
   m.def("hidden_dropout_mask(int rows, int H, float p, int seed, int offset, int row0=0) -> Tensor",
         &hidden_dropout_mask);
@@ -1805,6 +1835,7 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("swiglu_bwd", swiglu_bwd);
   m.impl("attn_fwd", attn_fwd);
   m.impl("attn_bwd", attn_bwd);
+  m.impl("segment_bounds", segment_bounds);
   m.impl("maxpool_bwd", maxpool_bwd);
   m.impl("conv1x1_fwd", conv1x1_fwd);
   m.impl("conv1x1_dgrad", conv1x1_dgrad);

@@ -160,7 +160,47 @@ def attention_seqlens_mask(seqlens: torch.Tensor, S: int, causal: bool) -> torch
     return m
 
 
-def attention(q, k, v, *, causal=True, scale=None, dropout_p=0.0, seqlens=None):
+def segment_bounds(ids: torch.Tensor) -> torch.Tensor:
+    """int32 [B, 2, S] document bounds of packed rows from integer ids [B, S], in plain torch ops (the
+    host mirror of K8's ``attn_segment_bounds_kernel``).  A document is a maximal run of equal
+    consecutive ids; ``[:, 0, s]`` is the index of the first token of token s's document, ``[:, 1, s]``
+    one past its last."""
+    if ids.dim() != 2 or ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError(f"segment ids must be an integer [B, S] tensor, got {tuple(ids.shape)} {ids.dtype}")
+    B, S = ids.shape
+    ids = ids.to(torch.int32)   # as the device path: ids are compared as int32 values (wider ones wrap)
+    pos = torch.arange(S, device=ids.device).expand(B, S)
+    start = torch.ones(B, S, dtype=torch.bool, device=ids.device)
+    start[:, 1:] = ids[:, 1:] != ids[:, :-1]
+    lo = torch.cummax(torch.where(start, pos, torch.zeros_like(pos)), dim=1).values
+    nxt = torch.full_like(pos, S)           # nxt[s] = s + 1 if a document starts there, else S
+    nxt[:, :-1] = torch.where(start[:, 1:], pos[:, 1:], nxt[:, 1:])
+    hi = torch.cummin(nxt.flip(1), dim=1).values.flip(1)
+    return torch.stack([lo, hi], dim=1).to(torch.int32)
+
+
+def _segments_bounds(segments: torch.Tensor, B: int, S: int) -> torch.Tensor:
+    """``segments`` as bounds [B, 2, S]: ids [B, S] are scanned, bounds are taken as they are."""
+    if segments.dim() == 2 and tuple(segments.shape) == (B, S):
+        return segment_bounds(segments)
+    if segments.dim() == 3 and tuple(segments.shape) == (B, 2, S) and not segments.is_floating_point():
+        return segments
+    raise ValueError(f"segments must be integer ids [B = {B}, S = {S}] or bounds [B, 2, S], got "
+                     f"{tuple(segments.shape)} {segments.dtype}")
+
+
+def attention_segments_mask(bounds: torch.Tensor, causal: bool) -> torch.Tensor:
+    """bool [B, 1, S, S] block-diagonal mask of packed rows from their bounds [B, 2, S] (True =
+    attend): query q sees the keys ``lo[q] <= k < hi[q]``, up to itself when causal."""
+    S = bounds.size(2)
+    kpos = torch.arange(S, device=bounds.device)[None, None, :]
+    m = (kpos >= bounds[:, 0, :, None]) & (kpos < bounds[:, 1, :, None])
+    if causal:
+        m = m & torch.ones(S, S, dtype=torch.bool, device=bounds.device).tril()
+    return m[:, None]
+
+
+def attention(q, k, v, *, causal=True, scale=None, dropout_p=0.0, seqlens=None, segments=None):
     """[B, S, H, D] / [B, S, Hkv, D] -> [B, S, H, D] via SDPA (fp32 oracle when given fp32).
     ``dropout_p`` is SDPA's own dropout (torch's mask, not K8's).  A ``scale`` that is not finite and
     positive is computed from plain ops in fp32 instead: SDPA's math path takes the square root of
@@ -169,11 +209,20 @@ def attention(q, k, v, *, causal=True, scale=None, dropout_p=0.0, seqlens=None):
     ``seqlens`` (integer [B]): a right-padded batch, K8's contract (:func:`madnn.ops.attention`).
     Padded positions of q, k and v are replaced by zeros with ``torch.where`` before anything is
     computed (their values, NaN included, reach no result and their gradients are exact zeros), valid
-    query rows see the valid keys only, and padded rows of the output are exact zeros."""
+    query rows see the valid keys only, and padded rows of the output are exact zeros.
+
+    ``segments`` (integer ids [B, S], or their :func:`segment_bounds` [B, 2, S]): packed rows, every
+    token attends inside its own document only (up to itself when causal), through the materialised
+    block-diagonal mask.  Not together with ``seqlens`` (``ValueError``): a padded tail is simply a
+    document of its own."""
     import torch.nn.functional as F
 
     h, hkv = q.size(2), k.size(2)
     mask = None
+    if segments is not None:
+        if seqlens is not None:
+            raise ValueError("attention: segments and seqlens exclude each other")
+        mask = attention_segments_mask(_segments_bounds(segments.to(q.device), q.size(0), q.size(1)), causal)
     if seqlens is not None:
         S = q.size(1)
         seqlens = seqlens.to(q.device)
