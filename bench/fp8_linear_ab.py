@@ -1,0 +1,104 @@
+"""FP8 Linear A/B: the fp8 forward (quantise x, quantise w with its transposed image, K17) against the bf16
+forward the same Linear runs without fp8, and the fp8 data gradient (quantise dy, K17 on the transposed weight
+image) against the bf16 one, on Llama-3 8B's four Linears at 8192 tokens and GPT-2 medium's c_proj at 131072.
+Both sides in one process, alternating round by round after warm-up, device events around ``reps`` calls.
+Per shape one JSON line: every piece in us (median over the rounds), K17 alone in TFLOP/s (2 M N K over its
+time), the quantisers in GB/s (bytes read + written over their time) and the end-to-end ratios fp8 / bf16
+(< 1: fp8 is faster).  ``--out`` also writes the whole record as one JSON file."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = [  # name, tokens, in-features, out-features
+    ("llama3-8b qkv", 8192, 4096, 6144), ("llama3-8b proj", 8192, 4096, 4096),
+    ("llama3-8b gate_up", 8192, 4096, 28672), ("llama3-8b down", 8192, 14336, 4096),
+    ("gpt2-medium c_proj", 131072, 4096, 1024),
+]
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps * 1e3
+
+
+def measure(name, M, K, N, reps, rounds):
+    from madnn import ops
+
+    k = torch.ops.madnn
+    x = torch.randn(M, K, device="cuda").bfloat16()
+    w = (torch.randn(N, K, device="cuda") * 0.02).bfloat16()
+    dy = torch.randn(M, N, device="cuda").bfloat16()
+    x8, _, sx = k.fp8_quant(x, 0, False)
+    w8, w8t, sw = k.fp8_quant(w, 0, True)
+    g8, _, sg = k.fp8_quant(dy, 1, False)
+
+    def fp8_fwd():
+        a8, _, sa = k.fp8_quant(x, 0, False)
+        b8, _, sb = k.fp8_quant(w, 0, True)
+        return k.fp8_gemm(a8, sa[1:], b8, sb[1:], None, None)
+
+    def fp8_dgrad():
+        a8, _, sa = k.fp8_quant(dy, 1, False)
+        return k.fp8_gemm(a8, sa[1:], w8t, sw[1:], None, None)
+
+    cases = {
+        "quant_x": lambda: k.fp8_quant(x, 0, False), "quant_w_t": lambda: k.fp8_quant(w, 0, True),
+        "quant_dy": lambda: k.fp8_quant(dy, 1, False),
+        "k17_fwd": lambda: k.fp8_gemm(x8, sx[1:], w8, sw[1:], None, None),
+        "k17_dgrad": lambda: k.fp8_gemm(g8, sg[1:], w8t, sw[1:], None, None),
+        "fp8_fwd": fp8_fwd, "bf16_fwd": lambda: torch.nn.functional.linear(x, w),
+        "fp8_dgrad": fp8_dgrad, "bf16_dgrad": lambda: ops.dgrad(dy, w),
+    }
+    for fn in cases.values():   # warm-up: code objects, library algorithm choice, dgrad's per-shape choice
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {n: [] for n in cases}
+    for _ in range(rounds):     # alternate all sides inside every round
+        for n, fn in cases.items():
+            us[n].append(timed(fn, reps))
+    med = {n: statistics.median(v) for n, v in us.items()}
+    flop = 2.0 * M * N * K
+    rec = {"shape": name, "M": M, "K": K, "N": N, "reps": reps, "rounds": rounds,
+           "us": {n: round(v, 1) for n, v in med.items()},
+           "us_min_max": {n: [round(min(v), 1), round(max(v), 1)] for n, v in us.items()},
+           "k17_fwd_tflops": round(flop / med["k17_fwd"] / 1e6, 1),
+           "k17_dgrad_tflops": round(flop / med["k17_dgrad"] / 1e6, 1),
+           "bf16_fwd_tflops": round(flop / med["bf16_fwd"] / 1e6, 1),
+           "quant_x_gbs": round(3.0 * M * K / med["quant_x"] / 1e3, 1),        # 2 B read + 1 B written per element
+           "quant_w_t_gbs": round(4.0 * N * K / med["quant_w_t"] / 1e3, 1),    # + the transposed image
+           "quant_dy_gbs": round(3.0 * M * N / med["quant_dy"] / 1e3, 1),
+           "fwd_ratio_fp8_over_bf16": round(med["fp8_fwd"] / med["bf16_fwd"], 3),
+           "dgrad_ratio_fp8_over_bf16": round(med["fp8_dgrad"] / med["bf16_dgrad"], 3)}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    from madnn import ops
+
+    assert torch.cuda.is_available() and ops.load_kernels(), "needs the GPU and the kernel library"
+    recs = [measure(*s, args.reps, args.rounds) for s in SHAPES]
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "records": recs}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

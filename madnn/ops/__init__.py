@@ -2324,14 +2324,123 @@ def gelu_mlp(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: 
     return _GeluMLPFn.apply(x, w1, b1, w2, b2, residual, GELU_KIND[approximate])
 
 
+# --------------------------------------------------------------------------- K17 (fp8 Linear)
+FP8_LINEAR = os.environ.get("MADNN_FP8_LINEAR", "0") != "0"  # ops.linear(fp8=None) takes the fp8 path (opt-in)
+_FP8_FMT = {"e4m3": 0, "e5m2": 1}
+
+
+def _fp8_rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as the 2-D bf16 matrix the quantiser reads: rows contiguous and 16-B aligned (a row stride stays)."""
+    t2 = t if t.dim() == 2 else t.reshape(-1, t.shape[-1])
+    if t2.stride(1) != 1 or t2.stride(0) % 8 or t2.stride(0) < t2.shape[1] or t2.data_ptr() % 16:
+        t2 = t2.contiguous()
+    return t2
+
+
+def fp8_quantize(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False):
+    """``(q, qt, scale)``: the 2-D bf16 ``x`` [R, C] scaled by a power of two taken from its own amax
+    (``reference.fp8_scale``) and cast to ``torch.float8_e4m3fn`` (``fmt="e4m3"``) or ``float8_e5m2``
+    (``"e5m2"``) with round-to-nearest-even; ``qt`` is the transposed image [C, R] written by the same
+    launch (``None`` unless ``transpose``), ``scale`` the 1-element fp32 tensor, formed on the device.
+    ``C % 16 == 0``, and ``R % 16 == 0`` with ``transpose``.  Plain torch on CPU tensors."""
+    if fmt not in _FP8_FMT:
+        raise ValueError(f"fp8_quantize: fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
+    if x.dim() != 2:
+        raise ValueError("fp8_quantize: x must be 2-D")
+    if not _is_dev(x):
+        q, scale = reference.fp8_quantize(x, fmt)
+        return q, (q.t().contiguous() if transpose else None), scale
+    q, qt, scales = _need_native("fp8_quantize").fp8_quant(_fp8_rows(x), _FP8_FMT[fmt], transpose)
+    return q, (qt if transpose else None), scales[:1]
+
+
+def fp8_gemm(a8: torch.Tensor, sa: torch.Tensor, b8: torch.Tensor, sb: torch.Tensor,
+             bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K17: bf16 ``(a8 / sa) @ (b8 / sb).T (+ bias) (+ residual)`` for fp8 ``a8`` [M, K] and ``b8`` [N, K]
+    (each e4m3fn or e5m2) with their 1-element fp32 scales; fp32 accumulation, one rounding.
+    ``K % 16 == 0`` and ``N % 8 == 0``.  Plain torch on CPU tensors."""
+    if not _is_dev(a8):
+        y = (a8.float() @ b8.float().t()) * (sa.reciprocal() * sb.reciprocal())
+        y = y + bias.float() if bias is not None else y
+        return (y + residual.float() if residual is not None else y).to(torch.bfloat16)
+    return _need_native("fp8_gemm").fp8_gemm(a8, sa.reciprocal(), b8, sb.reciprocal(), bias, residual)
+
+
+def fp8_linear_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Whether ``linear(x, weight, fp8=True)`` runs K17: HIP bf16 activation and weight, in- and
+    out-features multiples of 16, the kernel library loaded."""
+    return (_is_dev(x) and _is_dev(weight) and x.dtype == weight.dtype == torch.bfloat16 and weight.dim() == 2
+            and x.dim() >= 1 and x.shape[-1] == weight.shape[1] and x.numel() > 0
+            and weight.shape[0] % 16 == 0 and weight.shape[1] % 16 == 0 and load_kernels())
+
+
+class _LinearFp8Fn(torch.autograd.Function):
+    """y = x W^T + b (+ residual) with the forward and the data gradient on K17.
+
+    Forward: x -> e4m3, W -> e4m3 with its transposed image in the same launch, one K17 GEMM with bias
+    and residual in its epilogue.  Saved: bf16 x, the transposed fp8 weight and its scale.  Backward:
+    dy -> e5m2, dx = K17(dy8, w8t); the weight gradient is :func:`_weight_grad` on the bf16 tensors (grad
+    sink included), the bias gradient :func:`_out_bias_grad`, the residual's gradient dy itself -- all
+    three exactly as :class:`_LinearFn`."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual):
+        k = _need_native("fp8 linear")
+        n = weight.shape[0]
+        x8, _, sx = k.fp8_quant(_fp8_rows(x), 0, False)
+        w8, w8t, sw = k.fp8_quant(_fp8_rows(weight), 0, True)
+        res2 = residual.reshape(-1, n).contiguous() if residual is not None else None
+        y = k.fp8_gemm(x8, sx[1:], w8, sw[1:], bias, res2)
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        ctx.param = weight
+        ctx.has_res = residual is not None
+        ctx.save_for_backward(x, w8t, sw)
+        return y.view(*x.shape[:-1], n)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w8t, sw = ctx.saved_tensors
+        db = dx = dw = None
+        if ctx.bias_dtype is not None and ctx.needs_input_grad[2]:
+            db = _out_bias_grad(g, ctx.bias_dtype)
+        g2 = g.reshape(-1, g.shape[-1])
+        if not g2.is_contiguous():
+            g2 = g2.contiguous()
+        if ctx.needs_input_grad[0]:
+            k = _need_native("fp8 linear")
+            g8, _, sg = k.fp8_quant(g2, 1, False)
+            dx = k.fp8_gemm(g8, sg[1:], w8t, sw[1:], None, None).view(x.shape)
+        if ctx.needs_input_grad[1]:
+            dw = _weight_grad(g2, x.reshape(-1, x.shape[-1]), ctx.param)
+        ctx.param = None
+        return dx, dw, db, (g if ctx.has_res else None)
+
+
+def _fp8_linear_ok(x, weight, bias, residual) -> bool:
+    return (torch.is_grad_enabled() and fp8_linear_supported(x, weight)
+            and (bias is None or (_is_dev(bias) and bias.dtype in (torch.float32, torch.bfloat16)))
+            and (residual is None or (_is_dev(residual) and residual.dtype == torch.bfloat16
+                                      and residual.shape[-1] == weight.shape[0])))
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, gelu: bool = False,
-           force_fn: bool = False, residual: Optional[torch.Tensor] = None):
+           force_fn: bool = False, residual: Optional[torch.Tensor] = None, fp8: Optional[bool] = None):
     """``act(F.linear(x, weight, bias)) + residual`` with act in {identity, tanh-GELU}: one
     epilogue-fused hipBLASLt GEMM forward; backward fuses the bias gradient (K11) and writes the
     weight gradient into the reducer bucket (:func:`grad_sink`).  Eager ops on CPU tensors
-    (``force_fn`` runs the autograd Function anyway: tests of the sink path)."""
+    (``force_fn`` runs the autograd Function anyway: tests of the sink path).
+
+    ``fp8`` (``None``: the module switch ``FP8_LINEAR``, env ``MADNN_FP8_LINEAR``, default off): forward and
+    data gradient on the fp8 GEMM K17 (:class:`_LinearFp8Fn`) when ``gelu`` is false, gradients are enabled
+    and :func:`fp8_linear_supported` holds; in every other case the call is what it is without ``fp8``.
+    ``fp8=True`` on CPU tensors runs ``reference.linear_fp8`` (the same numerics in plain torch)."""
     if residual is not None and residual.shape[:-1] != x.shape[:-1]:
         raise ValueError("linear: residual must have the output's shape")
+    if (FP8_LINEAR if fp8 is None else fp8) and not gelu:
+        if fp8 and not _is_dev(x):
+            return reference.linear_fp8(x, weight, bias, residual)
+        if _fp8_linear_ok(x, weight, bias, residual):
+            return _LinearFp8Fn.apply(x, weight, bias, residual)
     if not torch.is_grad_enabled() or (not force_fn and (not _is_dev(x) or weight.shape[0] % 8)):
         if not torch.is_grad_enabled() and _is_dev(x) and (gelu or residual is not None) and weight.shape[0] % 8 == 0:
             out = _lt_epilogue(x, weight, bias, residual, gelu)
@@ -2352,6 +2461,7 @@ __all__ = [
     "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "conv1x1_tune", "stem_conv", "stem_supported", "stem_bn_relu_maxpool", "stem_bn_relu_maxpool_supported", "native_available", "native_tune", "load_kernels", "kernels_path", "hidden_supported", "reference",
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
+    "fp8_quantize", "fp8_gemm", "fp8_linear_supported", "FP8_LINEAR",
 ]
 
 if os.environ.get("MADNN_EAGER_LOAD", "0") == "1":

@@ -362,4 +362,19 @@ hipError_t madnn_dropout_add(const void* x, const void* res, void* out, int64_t 
 hipError_t madnn_hidden_dropout_mask(uint8_t* out, int64_t rows, int H, int64_t row0, uint32_t threshold,
                                      uint64_t seed, uint64_t offset, hipStream_t st);
 
+// ---- fp8.hip ----
+// fmt everywhere: 0 = e4m3fn, 1 = e5m2 (OCP; torch.float8_e4m3fn / float8_e5m2)
+// partial amax rows (floats of workspace) madnn_fp8_quant needs
+int madnn_fp8_quant_rows(int64_t R, int64_t C);
+// x: bf16 [R][C] with row stride ldx (elements) -> q: fp8 [R][C], qt (optional): fp8 [C][R];
+// scales: [2] fp32 = (scale, 1 / scale), the power of two formed on the device from x's amax.
+// C % 16 == 0, ldx % 8 == 0, 16-B aligned x; with qt also R % 16 == 0.
+hipError_t madnn_fp8_quant(const void* x, int64_t ldx, int64_t R, int64_t C, int fmt, void* q, void* qt,
+                           float* partial, float* scales, hipStream_t stream);
+// K17: out[M][N] (bf16) = (a[M][K] . b[N][K]^T) * inv_a[0] * inv_b[0] (+ bias[N]) (+ res[M][N]), a / b fp8 with
+// row strides lda / ldb; K % 16 == 0, N % 8 == 0, lda % 16 == 0, ldb % 16 == 0; out / res contiguous
+hipError_t madnn_fp8_gemm(const void* a, int fmt_a, const void* b, int fmt_b, const float* inv_a,
+                          const float* inv_b, const void* bias, int bias_f32, const void* res, void* out,
+                          int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, hipStream_t stream);
+
 }  // extern "C"

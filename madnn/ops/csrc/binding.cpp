@@ -1676,9 +1676,79 @@ void hwq_spin(const at::Tensor& like, int64_t spin_us) {
   check(madnn_hwq_spin(spin_us, cur_stream(like)), "hwq_spin");
 }
 
+// ---- K17 fp8 GEMM and its quantiser (fp8.hip) --------------------------------------------------
+int fp8_fmt(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kFloat8_e5m2, "fp8: ", name,
+              " must be float8_e4m3fn or float8_e5m2");
+  return t.scalar_type() == at::kFloat8_e5m2 ? 1 : 0;
+}
+
+void fp8_rows_check(const at::Tensor& t, const char* name, int64_t align) {
+  check_dev(t, name);
+  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1) && t.stride(0) % align == 0 &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "fp8: ", name, " must be 2-D with contiguous, 16-B aligned rows");
+}
+
+// x: bf16 [R, C] (row stride allowed) -> (q [R, C], qt [C, R] or empty, scales [2] = (scale, 1 / scale))
+std::tuple<at::Tensor, at::Tensor, at::Tensor> fp8_quant(const at::Tensor& x, int64_t fmt, bool transpose) {
+  fp8_rows_check(x, "x", 8);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "fp8_quant: x must be bf16");
+  TORCH_CHECK(fmt == 0 || fmt == 1, "fp8_quant: fmt 0 (e4m3fn) or 1 (e5m2)");
+  const int64_t R = x.size(0), C = x.size(1);
+  TORCH_CHECK(R > 0 && C > 0 && C % 16 == 0 && (!transpose || R % 16 == 0),
+              "fp8_quant: C % 16 == 0 (and R % 16 == 0 for the transposed image), got R=", R, " C=", C);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const auto qopt = x.options().dtype(fmt == 1 ? at::kFloat8_e5m2 : at::kFloat8_e4m3fn);
+  at::Tensor q = at::empty({R, C}, qopt);
+  at::Tensor qt = transpose ? at::empty({C, R}, qopt) : at::empty({0}, qopt);
+  at::Tensor partial = at::empty({madnn_fp8_quant_rows(R, C)}, x.options().dtype(at::kFloat));
+  at::Tensor scales = at::empty({2}, x.options().dtype(at::kFloat));
+  check(madnn_fp8_quant(x.data_ptr(), x.stride(0), R, C, (int)fmt, q.data_ptr(), transpose ? qt.data_ptr() : nullptr,
+                        partial.data_ptr<float>(), scales.data_ptr<float>(), cur_stream(x)),
+        "fp8_quant");
+  return {q, qt, scales};
+}
+
+// y [M, N] bf16 = (a8 [M, K] . b8 [N, K]^T) * inv_a * inv_b (+ bias) (+ res); inv_a / inv_b: device fp32 scalars
+at::Tensor fp8_gemm(const at::Tensor& a, const at::Tensor& inv_a, const at::Tensor& b, const at::Tensor& inv_b,
+                    const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res) {
+  fp8_rows_check(a, "a", 16);
+  fp8_rows_check(b, "b", 16);
+  const int fa = fp8_fmt(a, "a"), fb = fp8_fmt(b, "b");
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  TORCH_CHECK(b.size(1) == K && M > 0 && N > 0 && K > 0 && K % 16 == 0 && N % 8 == 0,
+              "fp8_gemm: a [M, K], b [N, K] with K % 16 == 0 and N % 8 == 0, got M=", M, " N=", N, " K=", K);
+  for (const at::Tensor* s : {&inv_a, &inv_b}) {
+    check_dev(*s, "scale");
+    TORCH_CHECK(s->scalar_type() == at::kFloat && s->numel() == 1, "fp8_gemm: scales are 1-element fp32 tensors");
+  }
+  const bool hb = bias.has_value() && bias->defined();
+  if (hb) {
+    check_dev(*bias, "bias");
+    TORCH_CHECK(bias->numel() == N && bias->is_contiguous() &&
+                    (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16),
+                "fp8_gemm: bias must be a contiguous fp32/bf16 [N]");
+  }
+  const bool hr = res.has_value() && res->defined();
+  if (hr) {
+    gemm_check(*res, "res");
+    TORCH_CHECK(res->numel() == M * N && res->size(-1) == N, "fp8_gemm: residual shape");
+  }
+  at::hip::HIPGuardMasqueradingAsCUDA guard(a.device());
+  at::Tensor y = at::empty({M, N}, a.options().dtype(at::kBFloat16));
+  check(madnn_fp8_gemm(a.data_ptr(), fa, b.data_ptr(), fb, inv_a.data_ptr<float>(), inv_b.data_ptr<float>(),
+                       hb ? bias->data_ptr() : nullptr, hb && bias->scalar_type() == at::kFloat ? 1 : 0,
+                       hr ? res->data_ptr() : nullptr, y.data_ptr(), M, N, K, a.stride(0), b.stride(0), cur_stream(a)),
+        "fp8_gemm");
+  return y;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(madnn, m) {
+  m.def("fp8_quant(Tensor x, int fmt, bool transpose) -> (Tensor, Tensor, Tensor)");
+  m.def("fp8_gemm(Tensor a, Tensor inv_a, Tensor b, Tensor inv_b, Tensor? bias, Tensor? res) -> Tensor");
   m.def("hwq_batch(Tensor kinds, Tensor msgs, Tensor(a!) a, Tensor(b!) b, int epoch, int timeout_us, Tensor(c!) ok, "
         "Tensor ok_index) -> ()");
   m.def("hwq_spin(Tensor like, int spin_us) -> ()");
@@ -1853,6 +1923,8 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("linear_wgrad4h", linear_wgrad4h);
   m.impl("linear_fwd_p", linear_fwd_p);
   m.impl("linear_dgrad_p", linear_dgrad_p);
+  m.impl("fp8_quant", fp8_quant);
+  m.impl("fp8_gemm", fp8_gemm);
   m.impl("conv3x3_fwd", conv3x3_fwd);
   m.impl("conv3x3_fwd_s2", conv3x3_fwd_s2);
   m.impl("conv3x3_wgrad", conv3x3_wgrad);

@@ -327,3 +327,67 @@ def hidden_dropout_mask(rows: int, H: int, p: float, seed: int, offset: int, row
     byts = (words[..., None] >> shifts) & np.uint64(0xFF)                   # [rows, block, word, byte]
     keep = (byts < np.uint64(thr)).reshape(rows, 16 * nb)[:, :H]
     return torch.from_numpy(np.ascontiguousarray(keep))
+
+
+# --------------------------------------------------------------------------- K17 (fp8 Linear)
+# format -> (torch dtype, largest finite value FMAX, EF with FMAX = 0.875 * 2^EF)
+FP8_FORMATS = {"e4m3": (torch.float8_e4m3fn, 448.0, 9), "e5m2": (torch.float8_e5m2, 57344.0, 16)}
+
+
+def fp8_scale(amax, fmt: str = "e4m3") -> torch.Tensor:
+    """The per-tensor scale of the fp8 path, fp32: ``2^floor(log2(FMAX / amax))``, formed from amax's
+    exponent and fraction without a rounded division (``amax = m 2^ea`` with m in [0.5, 1): the exponent is
+    ``EF - ea``, one less when ``m > 0.875``).  ``amax == 0`` gives 1; the exponent is clamped to +-126 so
+    that the scale and its reciprocal are normal fp32 numbers (a subnormal amax meets the clamp)."""
+    ef = FP8_FORMATS[fmt][2]
+    a = torch.as_tensor(amax).detach().to(torch.float32)
+    m, ea = torch.frexp(a)
+    e = ef - ea.to(torch.int32) - (m > 0.875).to(torch.int32)
+    e = torch.where(torch.isfinite(a), e, torch.full_like(e, -126)).clamp(-126, 126)
+    e = torch.where(a == 0, torch.zeros_like(e), e)
+    return ((e + 127) << 23).view(torch.float32)
+
+
+def fp8_quantize(x: torch.Tensor, fmt: str = "e4m3"):
+    """``(q, scale)``: ``x * scale`` (exact in fp32: the scale is a power of two) cast to the fp8 format
+    with round-to-nearest-even, and the 1-element fp32 scale of :func:`fp8_scale`."""
+    scale = fp8_scale(x.detach().abs().max(), fmt).reshape(1)
+    return (x.detach().to(torch.float32) * scale).to(FP8_FORMATS[fmt][0]), scale
+
+
+class _LinearFp8(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, residual):
+        acc = torch.float32 if x.dtype in (torch.bfloat16, torch.float16) else x.dtype
+        x8, sx = fp8_quantize(x, "e4m3")
+        w8, sw = fp8_quantize(w, "e4m3")
+        wd = w8.to(acc) / sw.to(acc)
+        y = (x8.to(acc) / sx.to(acc)) @ wd.t()
+        if b is not None:
+            y = y + b.to(acc)
+        if residual is not None:
+            y = y + residual.to(acc)
+        ctx.save_for_backward(x, wd)
+        ctx.meta = (acc, w.dtype, b.dtype if b is not None else None, residual is not None)
+        return y.to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wd = ctx.saved_tensors
+        acc, wdt, bdt, has_res = ctx.meta
+        g8, sg = fp8_quantize(g, "e5m2")
+        dx = ((g8.to(acc) / sg.to(acc)) @ wd).to(x.dtype)
+        g2, x2 = g.reshape(-1, g.shape[-1]).to(acc), x.reshape(-1, x.shape[-1]).to(acc)
+        dw = (g2.t() @ x2).to(wdt)
+        db = g2.sum(0).to(bdt) if bdt is not None else None
+        return dx, dw, db, (g if has_res else None)
+
+
+def linear_fp8(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The FP8 Linear of ``ops.linear(fp8=True)`` in plain torch, on any device and in any float dtype: the
+    forward multiplies the dequantised e4m3 images of ``x`` and ``w`` (accumulating in fp32, or in the
+    input's dtype when that is wider), adds bias and residual and rounds once; the data gradient multiplies
+    the dequantised e5m2 image of the output gradient with the same dequantised weight; the weight gradient
+    uses the unquantised tensors."""
+    return _LinearFp8.apply(x, w, b, residual)
