@@ -4,7 +4,10 @@ image) against the bf16 one, on Llama-3 8B's four Linears at 8192 tokens and GPT
 Both sides in one process, alternating round by round after warm-up, device events around ``reps`` calls.
 Per shape one JSON line: every piece in us (median over the rounds), K17 alone in TFLOP/s (2 M N K over its
 time), the quantisers in GB/s (bytes read + written over their time) and the end-to-end ratios fp8 / bf16
-(< 1: fp8 is faster).  ``--out`` also writes the whole record as one JSON file."""
+(< 1: fp8 is faster).  The weight gradient: K17W alone (its two fp8 images exist already in the fp8 path) against
+the bf16 weight gradient the Linear runs today (``ops.wgrad_into``, its tuned choice), with K17W's split count and
+the bytes of activation a Linear saves for its backward in both modes, computed from the shape.
+``--out`` also writes the whole record as one JSON file."""
 import argparse
 import json
 import os
@@ -43,6 +46,8 @@ def measure(name, M, K, N, reps, rounds):
     w8, w8t, sw = k.fp8_quant(w, 0, True)
     g8, _, sg = k.fp8_quant(dy, 1, False)
 
+    dw8, dw16 = torch.empty_like(w), torch.empty_like(w)
+
     def fp8_fwd():
         a8, _, sa = k.fp8_quant(x, 0, False)
         b8, _, sb = k.fp8_quant(w, 0, True)
@@ -59,6 +64,8 @@ def measure(name, M, K, N, reps, rounds):
         "k17_dgrad": lambda: k.fp8_gemm(g8, sg[1:], w8t, sw[1:], None, None),
         "fp8_fwd": fp8_fwd, "bf16_fwd": lambda: torch.nn.functional.linear(x, w),
         "fp8_dgrad": fp8_dgrad, "bf16_dgrad": lambda: ops.dgrad(dy, w),
+        "k17w_wgrad": lambda: k.fp8_wgrad(g8, sg[1:], x8, sx[1:], dw8, 0),
+        "bf16_wgrad": lambda: ops.wgrad_into(dy, x, dw16),
     }
     for fn in cases.values():   # warm-up: code objects, library algorithm choice, dgrad's per-shape choice
         for _ in range(3):
@@ -80,7 +87,13 @@ def measure(name, M, K, N, reps, rounds):
            "quant_w_t_gbs": round(4.0 * N * K / med["quant_w_t"] / 1e3, 1),    # + the transposed image
            "quant_dy_gbs": round(3.0 * M * N / med["quant_dy"] / 1e3, 1),
            "fwd_ratio_fp8_over_bf16": round(med["fp8_fwd"] / med["bf16_fwd"], 3),
-           "dgrad_ratio_fp8_over_bf16": round(med["fp8_dgrad"] / med["bf16_dgrad"], 3)}
+           "dgrad_ratio_fp8_over_bf16": round(med["fp8_dgrad"] / med["bf16_dgrad"], 3),
+           "k17w_wgrad_tflops": round(flop / med["k17w_wgrad"] / 1e6, 1),
+           "bf16_wgrad_tflops": round(flop / med["bf16_wgrad"] / 1e6, 1),
+           "bf16_wgrad_choice": ops._CHOICES["wgrad"].get(("linear", M, N, K), "lt"),
+           "k17w_splits": k.fp8_wgrad_splits(M, N, K),
+           "wgrad_ratio_k17w_over_bf16": round(med["k17w_wgrad"] / med["bf16_wgrad"], 3),
+           "saved_activation_bytes": {"fp8": 2 * M * K, "fp8_wgrad": M * K + 8}}   # bf16 x / e4m3 x8 + its scale pair
     print(json.dumps(rec), flush=True)
     return rec
 

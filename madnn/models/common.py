@@ -43,11 +43,12 @@ def linear(mod: nn.Module, x: torch.Tensor, gelu: bool = False, residual: torch.
     whose backward produces the bias gradient (and the GELU backward) in one K11 pass and writes
     the weight gradient straight into the data-parallel bucket; any other module (e.g. a
     tensor-parallel replacement) is called as is.  A ``madnn.nn.Fp8Linear`` is treated the same way with
-    ``fp8=True`` (forward and data gradient on K17, the residual in its epilogue); a ``gelu=True`` call stays
-    bf16, and so do ``ops.gelu_mlp`` and ``ops.linear_tee``, which have no fp8 path."""
+    its ``fp8_mode`` (forward and data gradient on K17, the residual in its epilogue; ``"wgrad"``: the weight
+    gradient on K17W); a ``gelu=True`` call stays bf16, and so do ``ops.gelu_mlp`` and ``ops.linear_tee``,
+    which have no fp8 path."""
     if ops.FUSED_LINEAR and type(mod) in (nn.Linear, Fp8Linear):
         return ops.linear(x, mod.weight, mod.bias, gelu=gelu, residual=residual,
-                          fp8=True if type(mod) is Fp8Linear else None)
+                          fp8=mod.fp8_mode if type(mod) is Fp8Linear else None)
     y = mod(x)
     y = F.gelu(y, approximate="tanh") if gelu else y
     return y + residual if residual is not None else y

@@ -2325,7 +2325,8 @@ def gelu_mlp(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: 
 
 
 # --------------------------------------------------------------------------- K17 (fp8 Linear)
-FP8_LINEAR = os.environ.get("MADNN_FP8_LINEAR", "0") != "0"  # ops.linear(fp8=None) takes the fp8 path (opt-in)
+# ops.linear(fp8=None) takes the fp8 path (opt-in): False, True, or "wgrad" (the weight gradient on K17W too)
+FP8_LINEAR = {"0": False, "wgrad": "wgrad"}.get(os.environ.get("MADNN_FP8_LINEAR", "0"), True)
 _FP8_FMT = {"e4m3": 0, "e5m2": 1}
 
 
@@ -2366,6 +2367,27 @@ def fp8_gemm(a8: torch.Tensor, sa: torch.Tensor, b8: torch.Tensor, sb: torch.Ten
     return _need_native("fp8_gemm").fp8_gemm(a8, sa.reciprocal(), b8, sb.reciprocal(), bias, residual)
 
 
+def fp8_wgrad(dy8: torch.Tensor, sg: torch.Tensor, x8: torch.Tensor, sx: torch.Tensor,
+              out: Optional[torch.Tensor] = None, splits: int = 0) -> torch.Tensor:
+    """K17W: bf16 ``(dy8 / sg).T @ (x8 / sx)`` for fp8 ``dy8`` [M, N] and ``x8`` [M, K] (each e4m3fn or e5m2,
+    the token index strided in both: transposed LDS reads, no transposed image) with their 1-element fp32
+    scales; fp32 accumulation, one rounding.  Any ``M``.  The kernel takes ``N % 16 == 0`` and ``K % 16 == 0``
+    (whole 16-B chunks per image row); an image with another column count is first copied into one padded
+    with zero columns to the next multiple of 16 (the Linear never needs that: ``fp8_linear_supported``).
+    ``out``: a contiguous bf16 [N, K] to write into; ``splits``: workgroups per output tile over the tokens
+    (0: the kernel's choice; deterministic for every value).  Plain torch on CPU tensors."""
+    if not _is_dev(dy8):
+        dw = ((dy8.float().t() @ x8.float()) * (sg.reciprocal() * sx.reciprocal())).to(torch.bfloat16)
+        return dw if out is None else out.copy_(dw)
+    k = _need_native("fp8_wgrad")
+    n, kk = dy8.shape[1], x8.shape[1]
+    if n % 16 or kk % 16:
+        pad = lambda t: F.pad(t.view(torch.uint8), (0, -t.shape[1] % 16)).view(t.dtype)  # noqa: E731
+        dw = k.fp8_wgrad(pad(dy8), sg.reciprocal(), pad(x8), sx.reciprocal(), None, splits)[:n, :kk]
+        return dw.contiguous() if out is None else out.copy_(dw)
+    return k.fp8_wgrad(dy8, sg.reciprocal(), x8, sx.reciprocal(), out, splits)
+
+
 def fp8_linear_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
     """Whether ``linear(x, weight, fp8=True)`` runs K17: HIP bf16 activation and weight, in- and
     out-features multiples of 16, the kernel library loaded."""
@@ -2381,10 +2403,14 @@ class _LinearFp8Fn(torch.autograd.Function):
     and residual in its epilogue.  Saved: bf16 x, the transposed fp8 weight and its scale.  Backward:
     dy -> e5m2, dx = K17(dy8, w8t); the weight gradient is :func:`_weight_grad` on the bf16 tensors (grad
     sink included), the bias gradient :func:`_out_bias_grad`, the residual's gradient dy itself -- all
-    three exactly as :class:`_LinearFn`."""
+    three exactly as :class:`_LinearFn`.
+
+    ``wgrad`` (``ops.linear(fp8="wgrad")``): the weight gradient runs on K17W from the two fp8 images the path
+    makes anyway -- saved is x8 [tokens, in] with its scale instead of the bf16 x (half the bytes), dy is
+    quantised once for both gradients, and dW goes into the reducer's bucket slot as in :func:`_weight_grad`."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual):
+    def forward(ctx, x, weight, bias, residual, wgrad=False):
         k = _need_native("fp8 linear")
         n = weight.shape[0]
         x8, _, sx = k.fp8_quant(_fp8_rows(x), 0, False)
@@ -2394,26 +2420,36 @@ class _LinearFp8Fn(torch.autograd.Function):
         ctx.bias_dtype = bias.dtype if bias is not None else None
         ctx.param = weight
         ctx.has_res = residual is not None
-        ctx.save_for_backward(x, w8t, sw)
+        ctx.wgrad, ctx.x_shape = wgrad, x.shape
+        ctx.save_for_backward(*((x8, sx, w8t, sw) if wgrad else (x, w8t, sw)))
         return y.view(*x.shape[:-1], n)
 
     @staticmethod
     def backward(ctx, g):
-        x, w8t, sw = ctx.saved_tensors
+        *xs, w8t, sw = ctx.saved_tensors
         db = dx = dw = None
         if ctx.bias_dtype is not None and ctx.needs_input_grad[2]:
             db = _out_bias_grad(g, ctx.bias_dtype)
         g2 = g.reshape(-1, g.shape[-1])
         if not g2.is_contiguous():
             g2 = g2.contiguous()
-        if ctx.needs_input_grad[0]:
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        if need_dx or (ctx.wgrad and need_dw):
             k = _need_native("fp8 linear")
             g8, _, sg = k.fp8_quant(g2, 1, False)
-            dx = k.fp8_gemm(g8, sg[1:], w8t, sw[1:], None, None).view(x.shape)
-        if ctx.needs_input_grad[1]:
-            dw = _weight_grad(g2, x.reshape(-1, x.shape[-1]), ctx.param)
+        if need_dx:
+            dx = k.fp8_gemm(g8, sg[1:], w8t, sw[1:], None, None).view(ctx.x_shape)
+        if need_dw and ctx.wgrad:
+            x8, sx = xs
+            sink = grad_sink(ctx.param)
+            if sink is not None and not (sink.dtype == torch.bfloat16 and sink.is_contiguous()
+                                         and sink.data_ptr() % 16 == 0):
+                sink = None
+            dw = k.fp8_wgrad(g8, sg[1:], x8, sx[1:], sink, 0)
+        elif need_dw:
+            dw = _weight_grad(g2, xs[0].reshape(-1, ctx.x_shape[-1]), ctx.param)
         ctx.param = None
-        return dx, dw, db, (g if ctx.has_res else None)
+        return dx, dw, db, (g if ctx.has_res else None), None
 
 
 def _fp8_linear_ok(x, weight, bias, residual) -> bool:
@@ -2424,7 +2460,7 @@ def _fp8_linear_ok(x, weight, bias, residual) -> bool:
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, gelu: bool = False,
-           force_fn: bool = False, residual: Optional[torch.Tensor] = None, fp8: Optional[bool] = None):
+           force_fn: bool = False, residual: Optional[torch.Tensor] = None, fp8=None):
     """``act(F.linear(x, weight, bias)) + residual`` with act in {identity, tanh-GELU}: one
     epilogue-fused hipBLASLt GEMM forward; backward fuses the bias gradient (K11) and writes the
     weight gradient into the reducer bucket (:func:`grad_sink`).  Eager ops on CPU tensors
@@ -2433,14 +2469,19 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     ``fp8`` (``None``: the module switch ``FP8_LINEAR``, env ``MADNN_FP8_LINEAR``, default off): forward and
     data gradient on the fp8 GEMM K17 (:class:`_LinearFp8Fn`) when ``gelu`` is false, gradients are enabled
     and :func:`fp8_linear_supported` holds; in every other case the call is what it is without ``fp8``.
-    ``fp8=True`` on CPU tensors runs ``reference.linear_fp8`` (the same numerics in plain torch)."""
+    ``fp8=True`` on CPU tensors runs ``reference.linear_fp8`` (the same numerics in plain torch).
+    ``fp8="wgrad"`` (``MADNN_FP8_LINEAR=wgrad``) is that path with the weight gradient on the fp8 GEMM K17W
+    as well: the backward keeps the e4m3 image of ``x`` instead of ``x`` (``reference.linear_fp8(wgrad=True)``)."""
     if residual is not None and residual.shape[:-1] != x.shape[:-1]:
         raise ValueError("linear: residual must have the output's shape")
-    if (FP8_LINEAR if fp8 is None else fp8) and not gelu:
+    mode = FP8_LINEAR if fp8 is None else fp8
+    if mode not in (None, False, True, "wgrad"):
+        raise ValueError(f"linear: fp8 must be None, a bool or 'wgrad', not {fp8!r}")
+    if mode and not gelu:
         if fp8 and not _is_dev(x):
-            return reference.linear_fp8(x, weight, bias, residual)
+            return reference.linear_fp8(x, weight, bias, residual, wgrad=mode == "wgrad")
         if _fp8_linear_ok(x, weight, bias, residual):
-            return _LinearFp8Fn.apply(x, weight, bias, residual)
+            return _LinearFp8Fn.apply(x, weight, bias, residual, mode == "wgrad")
     if not torch.is_grad_enabled() or (not force_fn and (not _is_dev(x) or weight.shape[0] % 8)):
         if not torch.is_grad_enabled() and _is_dev(x) and (gelu or residual is not None) and weight.shape[0] % 8 == 0:
             out = _lt_epilogue(x, weight, bias, residual, gelu)
@@ -2461,7 +2502,7 @@ __all__ = [
     "bn_relu_conv1x1_epi_supported", "bn2_conv3_bn3_add_relu", "bn2_conv3_bn3_supported", "bn2_conv3_bn3_add_bn_relu", "bn2_conv3_bn3_add_bn_relu_supported", "conv1x1_supported", "conv1x1_tune", "stem_conv", "stem_supported", "stem_bn_relu_maxpool", "stem_bn_relu_maxpool_supported", "native_available", "native_tune", "load_kernels", "kernels_path", "hidden_supported", "reference",
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
-    "fp8_quantize", "fp8_gemm", "fp8_linear_supported", "FP8_LINEAR",
+    "fp8_quantize", "fp8_gemm", "fp8_wgrad", "fp8_linear_supported", "FP8_LINEAR",
 ]
 
 if os.environ.get("MADNN_EAGER_LOAD", "0") == "1":

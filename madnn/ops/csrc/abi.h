@@ -376,5 +376,13 @@ hipError_t madnn_fp8_quant(const void* x, int64_t ldx, int64_t R, int64_t C, int
 hipError_t madnn_fp8_gemm(const void* a, int fmt_a, const void* b, int fmt_b, const float* inv_a,
                           const float* inv_b, const void* bias, int bias_f32, const void* res, void* out,
                           int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, hipStream_t stream);
+// workgroups per output tile K17W would choose (its fp32 workspace is splits x N x K floats when splits > 1)
+int madnn_fp8_wgrad_splits(int64_t M, int64_t N, int64_t K);
+// K17W: dw[N][K] (bf16, contiguous) = (sum_m dy8[m][n] x8[m][k]) * inv_g[0] * inv_x[0], dy8 [M][N] / x8 [M][K] fp8
+// with row strides ldg / ldx; any M > 0, N % 16 == 0, K % 16 == 0, ldg % 16 == 0, ldx % 16 == 0, 16-B aligned
+// pointers; splits >= 1 workgroups per tile, ws: splits x N x K fp32 when splits > 1, else unused
+hipError_t madnn_fp8_wgrad(const void* dy8, int fmt_g, const void* x8, int fmt_x, const float* inv_g,
+                           const float* inv_x, void* dw, float* ws, int splits, int64_t M, int64_t N, int64_t K,
+                           int64_t ldg, int64_t ldx, hipStream_t stream);
 
 }  // extern "C"

@@ -1744,11 +1744,47 @@ at::Tensor fp8_gemm(const at::Tensor& a, const at::Tensor& inv_a, const at::Tens
   return y;
 }
 
+// K17W: dw [N, K] bf16 = (dy8 [M, N]^T . x8 [M, K]) * inv_g * inv_x, into `out` when given; splits 0: the kernel's choice
+at::Tensor fp8_wgrad(const at::Tensor& dy8, const at::Tensor& inv_g, const at::Tensor& x8, const at::Tensor& inv_x,
+                     const c10::optional<at::Tensor>& out, int64_t splits) {
+  fp8_rows_check(dy8, "dy8", 16);
+  fp8_rows_check(x8, "x8", 16);
+  const int fg = fp8_fmt(dy8, "dy8"), fx = fp8_fmt(x8, "x8");
+  const int64_t M = dy8.size(0), N = dy8.size(1), K = x8.size(1);
+  TORCH_CHECK(x8.size(0) == M && M > 0 && N > 0 && K > 0 && N % 16 == 0 && K % 16 == 0 && splits >= 0 && splits <= 4096,
+              "fp8_wgrad: dy8 [M, N], x8 [M, K] with N % 16 == 0 and K % 16 == 0, got M=", M, " N=", N, " K=", K,
+              " splits=", splits);
+  for (const at::Tensor* s : {&inv_g, &inv_x}) {
+    check_dev(*s, "scale");
+    TORCH_CHECK(s->scalar_type() == at::kFloat && s->numel() == 1, "fp8_wgrad: scales are 1-element fp32 tensors");
+  }
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dy8.device());
+  at::Tensor dw;
+  if (out.has_value() && out->defined()) {
+    gemm_check(*out, "out");
+    TORCH_CHECK(out->scalar_type() == at::kBFloat16 && out->numel() == N * K, "fp8_wgrad: out must be bf16 and hold N x K");
+    dw = *out;
+  } else {
+    dw = at::empty({N, K}, dy8.options().dtype(at::kBFloat16));
+  }
+  const int sp = splits > 0 ? (int)splits : madnn_fp8_wgrad_splits(M, N, K);
+  at::Tensor ws = sp > 1 ? at::empty({sp, N, K}, dy8.options().dtype(at::kFloat)) : at::Tensor();
+  check(madnn_fp8_wgrad(dy8.data_ptr(), fg, x8.data_ptr(), fx, inv_g.data_ptr<float>(), inv_x.data_ptr<float>(),
+                        dw.data_ptr(), sp > 1 ? ws.data_ptr<float>() : nullptr, sp, M, N, K, dy8.stride(0),
+                        x8.stride(0), cur_stream(dy8)),
+        "fp8_wgrad");
+  return dw;
+}
+
+int64_t fp8_wgrad_splits(int64_t M, int64_t N, int64_t K) { return madnn_fp8_wgrad_splits(M, N, K); }
+
 }  // namespace
 
 TORCH_LIBRARY(madnn, m) {
   m.def("fp8_quant(Tensor x, int fmt, bool transpose) -> (Tensor, Tensor, Tensor)");
   m.def("fp8_gemm(Tensor a, Tensor inv_a, Tensor b, Tensor inv_b, Tensor? bias, Tensor? res) -> Tensor");
+  m.def("fp8_wgrad(Tensor dy8, Tensor inv_g, Tensor x8, Tensor inv_x, Tensor? out, int splits) -> Tensor");
+  m.def("fp8_wgrad_splits(int M, int N, int K) -> int", &fp8_wgrad_splits);
   m.def("hwq_batch(Tensor kinds, Tensor msgs, Tensor(a!) a, Tensor(b!) b, int epoch, int timeout_us, Tensor(c!) ok, "
         "Tensor ok_index) -> ()");
   m.def("hwq_spin(Tensor like, int spin_us) -> ()");
@@ -1925,6 +1961,7 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("linear_dgrad_p", linear_dgrad_p);
   m.impl("fp8_quant", fp8_quant);
   m.impl("fp8_gemm", fp8_gemm);
+  m.impl("fp8_wgrad", fp8_wgrad);
   m.impl("conv3x3_fwd", conv3x3_fwd);
   m.impl("conv3x3_fwd_s2", conv3x3_fwd_s2);
   m.impl("conv3x3_wgrad", conv3x3_wgrad);

@@ -1,5 +1,6 @@
 // K17 -- fp8 GEMM on v_mfma_f32_32x32x64_f8f6f4 for gfx950, and the per-tensor quantiser that feeds it:
 // the forward and the data gradient of an opt-in FP8 Linear (ops.linear(fp8=True), madnn.nn.Fp8Linear).
+// K17W, the weight gradient of that Linear on the same MFMA (ops.linear(fp8="wgrad")), has its own header below.
 //
 // Formats: OCP e4m3fn (activations, weights) and e5m2 (output gradients), bit for bit torch's
 // float8_e4m3fn / float8_e5m2.  Scaling is per tensor and current: scale = 2^floor(log2(FMAX / amax)) of the
@@ -379,6 +380,233 @@ hipError_t launch_gemm(const Args& p, int64_t grid, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------------------------- K17W
+// fp8 weight gradient: dW[N][K] (bf16) = (sum_m dy8[m][n] x8[m][k]) inv_g inv_x.  Both operands have the
+// reduction index (the token m) STRIDED: they are the row-major images the fp8 Linear already made (x8 in the
+// forward, dy8 for the data gradient), so this GEMM costs no quantiser pass and the Linear saves x8, not x.
+//
+// Geometry (K17's): 256 (n) x 256 (k) output tile per 512-thread workgroup; 8 waves = 2 (wr: 128-row n half) x
+// 4 (wc: 64-column k quarter); a wave owns 128 x 64 as 4 x 2 accumulators of 32 x 32.  A reduction step is 128
+// tokens = two MFMA steps of 64.  LDS: 2 stages x (dy image [128 tokens][256 B of n] + x image [128][256 B of
+// k]) = 2 x 64 KiB = 128 KiB.  Staging is K17's: LDS-DMA pieces of 1 KiB (here 4 token rows of 256 B), 8 per
+// wave and stage -- waves 0..3 the dy image, 4..7 the x image -- counted vmcnt(8) waits, the two-barrier ring.
+// A DMA lane whose token is past the workgroup's token range, or whose 16-B column chunk is past N (K), reads
+// g_zero16: M is any positive number, N and K any multiples of 16, and no out-of-bounds address is formed.
+//
+// Fragments: the MFMA wants per lane one output row (an n, or a k) and 32 reduction bytes, which sit 256 B
+// apart in the image.  ds_read_b64_tr_b8 gathers them: a 16-lane group reads an 8-token x 16-column block --
+// lane i of the group ADDRESSES the 8 bytes at token i >> 1, columns 8 (i & 1) .. + 7, and RECEIVES the 8
+// tokens of column i.  A fragment is four such reads (tokens 8q .. 8q + 7, q = 0..3, of the lane half's 32);
+// lane groups 0 / 1 (2 / 3) take columns 0..15 / 16..31 of the 32-wide block, lane half hh tokens 32 hh .. + 31
+// of the 64-deep MFMA step.  Which token lands in which byte of the 32 is the same for both operands (same map,
+// same code), so a token meets itself; only the ownership of rows and columns has to be right, and
+// tests/test_fp8_wgrad_gpu.py (exact on small integers) is the proof.
+// Operand order: the MFMA's first operand is the x (k) fragment and its second the dy (n) fragment, so
+// register r of lane l holds dW[n = l & 31][k = 8 (r >> 2) + 4 (l >> 5) + (r & 3)] of its block: the register
+// quad runs along k, the contiguous output dimension.  cbsz carries x's format, blgp dy's.
+//
+// Swizzle: an image row is 256 B = all 64 banks, so unswizzled the 8 token rows of one transposed read would
+// land on the same 4 banks (8-way conflict).  16-B slot s of token row r holds chunk s ^ 2 (r & 7), applied to
+// the per-lane DMA source column and to the read address.  A 32-lane half of one read touches token rows
+// r0 .. r0 + 7 (r0 % 8 == 0) and the chunk pair {c, c + 1}, c even: the slots are {c ^ 2j, (c ^ 2j) + 1} for
+// j = 0..7 -- the XOR moves bits 1..3 only, so the eight pairs are the eight distinct aligned pairs of the 16
+// slots: 256 B on 64 different banks, conflict-free whether the LDS serves the read 16 or 32 lanes at a time.
+// The XOR term depends on the lane only (token row & 7 = (lane & 15) >> 1), so s, q and the stage are
+// immediate offsets of one per-lane address per fragment.
+//
+// Split over tokens: a weight gradient has few tiles and a long reduction, so `splits` workgroups share a
+// tile, each reducing a contiguous range of whole 128-token steps.  splits == 1: acc * (inv_g inv_x) through
+// LDS as fp32 (K17's staging) and out as 16-B bf16 stores.  splits > 1: the same staging, raw fp32 partial sums
+// to slab [split][N][K] in 1-KiB runs; wgrad8_reduce_kernel adds the slabs in split order, scales and rounds
+// once.  No float atomics: results are deterministic.
+constexpr int kWT = 128;                   // tokens per reduction step
+constexpr int kWRow = 256;                 // bytes per image row (the n or k tile)
+constexpr int kWImage = kWT * kWRow;       // 32 KiB
+constexpr int kWStage = 2 * kWImage;       // dy image, x image
+static_assert(2 * kWStage == kLds, "K17W uses K17's LDS budget");
+
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) i32x2 lds_i32x2;
+
+struct WArgs {
+  const uint8_t* g;      // dy8 [M][N]
+  const uint8_t* x;      // x8 [M][K]
+  uint16_t* out;         // [N][K] bf16 (splits == 1)
+  float* ws;             // [splits][N][K] fp32 (splits > 1)
+  const float* inv_g;
+  const float* inv_x;
+  int64_t ldg, ldx;
+  int64_t M, N, K;
+  int n_tiles, k_tiles, splits;
+  int steps_per;         // 128-token steps per split
+};
+
+// lane part of a fragment's read address for the 32 columns from c0 (header: Fragments, Swizzle)
+__device__ __forceinline__ int tr_lane_off(int c0, int lane) {
+  const int i = lane & 15, r7 = i >> 1;
+  const int slot = ((c0 >> 4) + ((lane >> 4) & 1)) ^ (2 * r7);
+  return (32 * (lane >> 5) + r7) * kWRow + 16 * slot + 8 * (i & 1);
+}
+
+// the 32 tokens of MFMA step s that this lane holds of its column: four ds_read_b64_tr_b8
+__device__ __forceinline__ i32x8 frag_tr(const uint8_t* img, int lane_off, int s) {
+  const uint8_t* p = img + lane_off + 64 * s * kWRow;
+  const i32x2 q0 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p));
+  const i32x2 q1 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p + 8 * kWRow));
+  const i32x2 q2 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p + 16 * kWRow));
+  const i32x2 q3 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p + 24 * kWRow));
+  return i32x8{q0[0], q0[1], q1[0], q1[1], q2[0], q2[1], q3[0], q3[1]};
+}
+
+// FG / FX: format flags of dy8 and x8
+template <int FG, int FX>
+__global__ __launch_bounds__(kThreads) void wgrad_kernel(const WArgs p) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[kLds];
+  const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, l32 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 2, wc = wave & 3;
+
+  // XCD-grouped logical id, tile fastest: an XCD's workgroups reduce the same tokens, whose rows they share in L2
+  const int wid = xcd_group_id(blockIdx.x, gridDim.x);
+  const int tiles = p.n_tiles * p.k_tiles;
+  const int split = wid / tiles, tile = wid - split * tiles;
+  const int64_t n0 = (int64_t)(tile / p.k_tiles) * kT, k0 = (int64_t)(tile % p.k_tiles) * kT;
+  const int64_t mbeg = (int64_t)split * p.steps_per * kWT;
+  int64_t mend = mbeg + (int64_t)p.steps_per * kWT;
+  mend = mend < p.M ? mend : p.M;
+  const int nk = mend > mbeg ? (int)((mend - mbeg + kWT - 1) / kWT) : 0;
+
+  // DMA sources: piece e of wave w covers token rows 32 (w & 3) + 4 e .. + 3 of the step, lane l of it row
+  // + (l >> 4), LDS slot l & 15 = chunk (l & 15) ^ 2 (row & 7), row & 7 = 4 (e & 1) + (l >> 4)
+  const bool is_g = wave < 4;
+  const uint8_t* const op = is_g ? p.g : p.x;
+  const int64_t ld = is_g ? p.ldg : p.ldx;
+  const int64_t c0 = is_g ? n0 : k0, clim = is_g ? p.N : p.K;
+  const int64_t col_even = c0 + 16 * ((lane & 15) ^ (2 * (lane >> 4)));
+  const int64_t col_odd = c0 + 16 * ((lane & 15) ^ (2 * (4 + (lane >> 4))));
+  const bool ok_even = col_even < clim, ok_odd = col_odd < clim;
+  const int row0 = 32 * (wave & 3) + (lane >> 4);
+  uint8_t* const dma_dst = smem + (is_g ? 0 : kWImage) + (wave & 3) * (kPieces * 1024);
+
+  // step t -> stage t & 1; a lane whose token or column chunk is outside reads the zero block
+  auto stage = [&](int t) {
+    const int64_t mb = mbeg + (int64_t)t * kWT + row0;
+#pragma unroll
+    for (int e = 0; e < kPieces; ++e) {
+      const int64_t m = mb + 4 * e;
+      const bool in = m < mend && ((e & 1) ? ok_odd : ok_even);
+      const void* s = in ? (const void*)(op + m * ld + ((e & 1) ? col_odd : col_even)) : (const void*)g_zero16;
+      glds16(s, (lds_void*)(dma_dst + (t & 1) * kWStage + e * 1024));
+    }
+  };
+
+  int goff[4], xoff[2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) goff[a] = tr_lane_off(wr * 128 + 32 * a, lane);
+#pragma unroll
+  for (int b = 0; b < 2; ++b) xoff[b] = tr_lane_off(wc * 64 + 32 * b, lane);
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = zero16();
+
+  if (nk > 0) stage(0);
+  for (int t = 0; t < nk; ++t) {
+    if (t + 1 < nk) {
+      stage(t + 1);
+      wait_vmcnt<kPieces>();  // step t's pieces: all but the 8 just issued
+    } else {
+      wait_vmcnt<0>();
+    }
+    barrier();
+    const uint8_t* sg = smem + (t & 1) * kWStage;
+    const uint8_t* sx = sg + kWImage;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      i32x8 xf[2], gf[4];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) xf[b] = frag_tr(sx, xoff[b], s);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) gf[a] = frag_tr(sg, goff[a], s);
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = mfma8<FG, FX>(xf[b], gf[a], acc[a][b]);
+    }
+    wait_lgkmcnt0();  // this stage's last fragment reads, before the barrier that opens it for step t + 2
+    barrier();
+  }
+
+  // ---- epilogue (header): two 128-row n halves through LDS as fp32, then rows of 8 k per lane
+  const bool slab = p.splits > 1;
+  const float sc = slab ? 1.f : p.inv_g[0] * p.inv_x[0];
+  char* ot = reinterpret_cast<char*>(smem);
+  const int c = tid & 31, rr = tid >> 5;
+  const int64_t kg = k0 + 8 * c;
+  float* const ws = slab ? p.ws + (int64_t)split * p.N * p.K : nullptr;
+#pragma unroll 1
+  for (int half = 0; half < 2; ++half) {
+    if (wr == half) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int nl = 32 * a + l32, ch = wc * 16 + 8 * b + 2 * g + hh;
+            const f32x16& v = acc[a][b];
+            *reinterpret_cast<f32x4*>(ot + nl * 1024 + 16 * (ch ^ (nl & 15))) =
+                f32x4{v[4 * g] * sc, v[4 * g + 1] * sc, v[4 * g + 2] * sc, v[4 * g + 3] * sc};
+          }
+    }
+    __syncthreads();
+    if (kg < p.K) {
+#pragma unroll 2
+      for (int i = 0; i < 8; ++i) {
+        const int nl = rr + 16 * i;
+        const int64_t ng = n0 + 128 * half + nl;
+        if (ng >= p.N) break;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(ot + nl * 1024 + 16 * ((2 * c) ^ (nl & 15)));
+        const f32x4 hi = *reinterpret_cast<const f32x4*>(ot + nl * 1024 + 16 * ((2 * c + 1) ^ (nl & 15)));
+        if (slab) {
+          *reinterpret_cast<f32x4*>(ws + ng * p.K + kg) = lo;
+          *reinterpret_cast<f32x4*>(ws + ng * p.K + kg + 4) = hi;
+        } else {
+          const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          store8<kBF16>(p.out, ng * p.K + kg, v);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// out[e] = bf16((sum_s ws[s][e]) inv_g inv_x), slabs added in split order; 8 elements per lane, 16-B accesses
+__global__ __launch_bounds__(256) void wgrad8_reduce_kernel(const float* __restrict__ ws, uint16_t* __restrict__ out,
+                                                            int splits, int64_t n, const float* __restrict__ inv_g,
+                                                            const float* __restrict__ inv_x) {
+  const float sc = inv_g[0] * inv_x[0];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 8;
+  for (int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8; e < n; e += stride) {
+    f32x4 lo = *reinterpret_cast<const f32x4*>(ws + e), hi = *reinterpret_cast<const f32x4*>(ws + e + 4);
+    for (int q = 1; q < splits; ++q) {
+      lo += *reinterpret_cast<const f32x4*>(ws + (int64_t)q * n + e);
+      hi += *reinterpret_cast<const f32x4*>(ws + (int64_t)q * n + e + 4);
+    }
+    const float v[8] = {lo[0] * sc, lo[1] * sc, lo[2] * sc, lo[3] * sc, hi[0] * sc, hi[1] * sc, hi[2] * sc, hi[3] * sc};
+    store8<kBF16>(out, e, v);
+  }
+}
+
+template <int FG, int FX>
+hipError_t launch_wgrad(const WArgs& p, hipStream_t s) {
+  const int64_t grid = (int64_t)p.n_tiles * p.k_tiles * p.splits;
+  hipLaunchKernelGGL((wgrad_kernel<FG, FX>), dim3((unsigned)grid), dim3(kThreads), 0, s, p);
+  return hipGetLastError();
+}
+
 }  // namespace fp8
 }  // namespace madnn
 
@@ -439,4 +667,67 @@ extern "C" hipError_t madnn_fp8_gemm(const void* a, int fmt_a, const void* b, in
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   if (fmt_a == 0) return fmt_b == 0 ? fp8::launch_gemm<0, 0>(p, grid, stream) : fp8::launch_gemm<0, 1>(p, grid, stream);
   return fmt_b == 0 ? fp8::launch_gemm<1, 0>(p, grid, stream) : fp8::launch_gemm<1, 1>(p, grid, stream);
+}
+
+// Workgroups per output tile for K17W: 256 CUs, one 128-KiB-LDS workgroup per CU.  Model, as madnn_wgrad_splits:
+// rounds of 256 workgroups x 128-token steps per split + the fp32 slab round trip (splits x N x K x 8 B);
+// a split keeps >= 4 steps.  The constants are UNMEASURED estimates: 1.8 us per 256^2 x 128 step (twice the
+// bf16 MFMA rate, ~2.4 PF/s) and ~5 TB/s for the slabs (bench/fp8_linear_ab.py records what they give).
+extern "C" int madnn_fp8_wgrad_splits(int64_t M, int64_t N, int64_t K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 1;
+  const int64_t tiles = ((N + fp8::kT - 1) / fp8::kT) * ((K + fp8::kT - 1) / fp8::kT);
+  const int64_t steps = (M + fp8::kWT - 1) / fp8::kWT;
+  int best = 1;
+  double best_t = 1e30;
+  for (int sp = 1; sp <= 256; ++sp) {
+    if (sp > 1 && steps / sp < 4) break;
+    const int64_t per = (steps + sp - 1) / sp;
+    const int64_t rounds = (tiles * sp + kNumCU - 1) / kNumCU;
+    const double t = rounds * per * 1.8 + (sp > 1 ? sp * (double)N * K * 8.0 / 5.0e6 : 0.0);
+    if (t < best_t * 0.98) {
+      best_t = t;
+      best = sp;
+    }
+  }
+  return best;
+}
+
+extern "C" hipError_t madnn_fp8_wgrad(const void* dy8, int fmt_g, const void* x8, int fmt_x, const float* inv_g,
+                                      const float* inv_x, void* dw, float* ws, int splits, int64_t M, int64_t N,
+                                      int64_t K, int64_t ldg, int64_t ldx, hipStream_t stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || N % 16 || K % 16 || ldg % 16 || ldx % 16 || ldg < N || ldx < K)
+    return hipErrorInvalidValue;
+  if ((fmt_g != 0 && fmt_g != 1) || (fmt_x != 0 && fmt_x != 1) || splits < 1) return hipErrorInvalidValue;
+  if (dy8 == nullptr || x8 == nullptr || dw == nullptr || inv_g == nullptr || inv_x == nullptr) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(dy8) | reinterpret_cast<uintptr_t>(x8) | reinterpret_cast<uintptr_t>(dw) |
+       reinterpret_cast<uintptr_t>(ws)) % 16)
+    return hipErrorInvalidValue;
+  if (splits > 1 && ws == nullptr) return hipErrorInvalidValue;
+  const int64_t steps = (M + fp8::kWT - 1) / fp8::kWT;
+  fp8::WArgs p;
+  p.g = static_cast<const uint8_t*>(dy8);
+  p.x = static_cast<const uint8_t*>(x8);
+  p.out = static_cast<uint16_t*>(dw);
+  p.inv_g = inv_g;
+  p.inv_x = inv_x;
+  p.ldg = ldg;
+  p.ldx = ldx;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.n_tiles = (int)((N + fp8::kT - 1) / fp8::kT);
+  p.k_tiles = (int)((K + fp8::kT - 1) / fp8::kT);
+  p.splits = (int)(splits < steps ? splits : steps);  // no split without a step; the slabs beyond stay unused
+  p.steps_per = (int)((steps + p.splits - 1) / p.splits);
+  p.splits = (int)((steps + p.steps_per - 1) / p.steps_per);
+  p.ws = p.splits > 1 ? ws : nullptr;
+  if ((int64_t)p.n_tiles * p.k_tiles * p.splits > 0x7fffffff) return hipErrorInvalidValue;
+  hipError_t e;
+  if (fmt_g == 0) e = fmt_x == 0 ? fp8::launch_wgrad<0, 0>(p, stream) : fp8::launch_wgrad<0, 1>(p, stream);
+  else e = fmt_x == 0 ? fp8::launch_wgrad<1, 0>(p, stream) : fp8::launch_wgrad<1, 1>(p, stream);
+  if (e != hipSuccess || p.splits == 1) return e;
+  const int64_t n = N * K;
+  hipLaunchKernelGGL(fp8::wgrad8_reduce_kernel, dim3((unsigned)stream_grid(n / 8, 256, 2048)), dim3(256), 0, stream,
+                     p.ws, p.out, p.splits, n, inv_g, inv_x);
+  return hipGetLastError();
 }

@@ -357,7 +357,7 @@ def fp8_quantize(x: torch.Tensor, fmt: str = "e4m3"):
 
 class _LinearFp8(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, residual):
+    def forward(ctx, x, w, b, residual, wgrad=False):
         acc = torch.float32 if x.dtype in (torch.bfloat16, torch.float16) else x.dtype
         x8, sx = fp8_quantize(x, "e4m3")
         w8, sw = fp8_quantize(w, "e4m3")
@@ -367,27 +367,30 @@ class _LinearFp8(torch.autograd.Function):
             y = y + b.to(acc)
         if residual is not None:
             y = y + residual.to(acc)
-        ctx.save_for_backward(x, wd)
-        ctx.meta = (acc, w.dtype, b.dtype if b is not None else None, residual is not None)
+        # with wgrad the backward sees the dequantised e4m3 image of x, not x
+        ctx.save_for_backward(x8.to(acc) / sx.to(acc) if wgrad else x, wd)
+        ctx.meta = (acc, x.dtype, w.dtype, b.dtype if b is not None else None, residual is not None, wgrad)
         return y.to(x.dtype)
 
     @staticmethod
     def backward(ctx, g):
         x, wd = ctx.saved_tensors
-        acc, wdt, bdt, has_res = ctx.meta
+        acc, xdt, wdt, bdt, has_res, wgrad = ctx.meta
         g8, sg = fp8_quantize(g, "e5m2")
-        dx = ((g8.to(acc) / sg.to(acc)) @ wd).to(x.dtype)
+        gd = g8.to(acc) / sg.to(acc)
+        dx = (gd @ wd).to(xdt)
         g2, x2 = g.reshape(-1, g.shape[-1]).to(acc), x.reshape(-1, x.shape[-1]).to(acc)
-        dw = (g2.t() @ x2).to(wdt)
+        dw = ((gd.reshape(-1, g.shape[-1]) if wgrad else g2).t() @ x2).to(wdt)
         db = g2.sum(0).to(bdt) if bdt is not None else None
-        return dx, dw, db, (g if has_res else None)
+        return dx, dw, db, (g if has_res else None), None
 
 
 def linear_fp8(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
-               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+               residual: Optional[torch.Tensor] = None, wgrad: bool = False) -> torch.Tensor:
     """The FP8 Linear of ``ops.linear(fp8=True)`` in plain torch, on any device and in any float dtype: the
     forward multiplies the dequantised e4m3 images of ``x`` and ``w`` (accumulating in fp32, or in the
     input's dtype when that is wider), adds bias and residual and rounds once; the data gradient multiplies
     the dequantised e5m2 image of the output gradient with the same dequantised weight; the weight gradient
-    uses the unquantised tensors."""
-    return _LinearFp8.apply(x, w, b, residual)
+    uses the unquantised tensors -- or, with ``wgrad`` (``ops.linear(fp8="wgrad")``, K17W), the same two
+    dequantised images: ``dW = (dy8 / sg)^T @ (x8 / sx)``, accumulated likewise and rounded once."""
+    return _LinearFp8.apply(x, w, b, residual, wgrad)
