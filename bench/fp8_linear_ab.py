@@ -7,6 +7,10 @@ time), the quantisers in GB/s (bytes read + written over their time) and the end
 (< 1: fp8 is faster).  The weight gradient: K17W alone (its two fp8 images exist already in the fp8 path) against
 the bf16 weight gradient the Linear runs today (``ops.wgrad_into``, its tuned choice), with K17W's split count and
 the bytes of activation a Linear saves for its backward in both modes, computed from the shape.
+The MX side (``fp8="mx"``): the one-pass block quantiser against the three-launch per-tensor one on x, W (with the
+second image) and dy, K17X against K17 on images made beforehand, and the MX forward and data gradient end to end
+against the per-tensor ones and against bf16; ``k17_spread`` is K17's own max / min over the rounds, the
+run-to-run spread a K17X / K17 ratio has to be read against.
 ``--out`` also writes the whole record as one JSON file."""
 import argparse
 import json
@@ -46,6 +50,10 @@ def measure(name, M, K, N, reps, rounds):
     w8, w8t, sw = k.fp8_quant(w, 0, True)
     g8, _, sg = k.fp8_quant(dy, 1, False)
 
+    mx8, mex, _, _ = k.mx_quant(x, 0, False)
+    mw8, mew, mw8t, mewt = k.mx_quant(w, 0, True)
+    mg8, meg, _, _ = k.mx_quant(dy, 0, False)
+
     dw8, dw16 = torch.empty_like(w), torch.empty_like(w)
 
     def fp8_fwd():
@@ -57,6 +65,15 @@ def measure(name, M, K, N, reps, rounds):
         a8, _, sa = k.fp8_quant(dy, 1, False)
         return k.fp8_gemm(a8, sa[1:], w8t, sw[1:], None, None)
 
+    def mx_fwd():
+        a8, ea, _, _ = k.mx_quant(x, 0, False)
+        b8, eb, _, _ = k.mx_quant(w, 0, True)
+        return k.mx_gemm(a8, ea, b8, eb, None, None)
+
+    def mx_dgrad():
+        a8, ea, _, _ = k.mx_quant(dy, 0, False)
+        return k.mx_gemm(a8, ea, mw8t, mewt, None, None)
+
     cases = {
         "quant_x": lambda: k.fp8_quant(x, 0, False), "quant_w_t": lambda: k.fp8_quant(w, 0, True),
         "quant_dy": lambda: k.fp8_quant(dy, 1, False),
@@ -66,6 +83,11 @@ def measure(name, M, K, N, reps, rounds):
         "fp8_dgrad": fp8_dgrad, "bf16_dgrad": lambda: ops.dgrad(dy, w),
         "k17w_wgrad": lambda: k.fp8_wgrad(g8, sg[1:], x8, sx[1:], dw8, 0),
         "bf16_wgrad": lambda: ops.wgrad_into(dy, x, dw16),
+        "mx_quant_x": lambda: k.mx_quant(x, 0, False), "mx_quant_w_t": lambda: k.mx_quant(w, 0, True),
+        "mx_quant_dy": lambda: k.mx_quant(dy, 0, False),
+        "k17x_fwd": lambda: k.mx_gemm(mx8, mex, mw8, mew, None, None),
+        "k17x_dgrad": lambda: k.mx_gemm(mg8, meg, mw8t, mewt, None, None),
+        "mx_fwd": mx_fwd, "mx_dgrad": mx_dgrad,
     }
     for fn in cases.values():   # warm-up: code objects, library algorithm choice, dgrad's per-shape choice
         for _ in range(3):
@@ -93,6 +115,12 @@ def measure(name, M, K, N, reps, rounds):
            "bf16_wgrad_choice": ops._CHOICES["wgrad"].get(("linear", M, N, K), "lt"),
            "k17w_splits": k.fp8_wgrad_splits(M, N, K),
            "wgrad_ratio_k17w_over_bf16": round(med["k17w_wgrad"] / med["bf16_wgrad"], 3),
+           "mx_quant_over_fp8_quant": {n: round(med["mx_quant_" + n] / med["quant_" + n], 3) for n in ("x", "w_t", "dy")},
+           "k17x_over_k17": {n: round(med["k17x_" + n] / med["k17_" + n], 3) for n in ("fwd", "dgrad")},
+           "k17_spread": {n: round(max(us["k17_" + n]) / min(us["k17_" + n]), 3) for n in ("fwd", "dgrad")},
+           "k17x_fwd_tflops": round(flop / med["k17x_fwd"] / 1e6, 1),
+           "mx_over_fp8": {n: round(med["mx_" + n] / med["fp8_" + n], 3) for n in ("fwd", "dgrad")},
+           "mx_over_bf16": {n: round(med["mx_" + n] / med["bf16_" + n], 3) for n in ("fwd", "dgrad")},
            "saved_activation_bytes": {"fp8": 2 * M * K, "fp8_wgrad": M * K + 8}}   # bf16 x / e4m3 x8 + its scale pair
     print(json.dumps(rec), flush=True)
     return rec

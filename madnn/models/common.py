@@ -44,7 +44,7 @@ def linear(mod: nn.Module, x: torch.Tensor, gelu: bool = False, residual: torch.
     the weight gradient straight into the data-parallel bucket; any other module (e.g. a
     tensor-parallel replacement) is called as is.  A ``madnn.nn.Fp8Linear`` is treated the same way with
     its ``fp8_mode`` (forward and data gradient on K17, the residual in its epilogue; ``"wgrad"``: the weight
-    gradient on K17W); a ``gelu=True`` call stays bf16, and so do ``ops.gelu_mlp`` and ``ops.linear_tee``,
+    gradient on K17W; ``"mx"``: the MX recipe on K17X); a ``gelu=True`` call stays bf16, and so do ``ops.gelu_mlp`` and ``ops.linear_tee``,
     which have no fp8 path."""
     if ops.FUSED_LINEAR and type(mod) in (nn.Linear, Fp8Linear):
         return ops.linear(x, mod.weight, mod.bias, gelu=gelu, residual=residual,

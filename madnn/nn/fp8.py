@@ -1,11 +1,13 @@
-"""FP8 Linear layers: the forward and the data gradient on the fp8 GEMM K17 (``ops.linear(fp8=True)``), and on
-request the weight gradient on K17W as well (``fp8="wgrad"``).
+"""FP8 Linear layers: the forward and the data gradient on the fp8 GEMM K17 (``ops.linear(fp8=True)``), on
+request the weight gradient on K17W as well (``fp8="wgrad"``), or the MX block-scaled recipe on K17X (``fp8="mx"``).
 
 :class:`Fp8Linear` is ``nn.Linear`` with another forward: same parameters, same state-dict keys, so a model
 converts in place (:func:`use_fp8_linears`) and its checkpoints interchange with the bf16 model's.  Scaling is
 per tensor and current (``ops.fp8_quantize``); the weight gradient stays a bf16 GEMM unless the module's
 ``fp8_mode`` is ``"wgrad"``, which also halves the activation the Linear saves (the e4m3 image instead of bf16).
-Not built: delayed scaling / amax history, block or MX scaling, a cache of the quantised weight across
+``fp8_mode = "mx"`` swaps the recipe: one E8M0 scale per 32 elements along the reduction (``ops.mx_quantize``, one
+launch and no global amax), all three operands e4m3, the scaling done by the MFMA in K17X.
+Not built: delayed scaling / amax history, an MX weight gradient, a cache of the quantised weight across
 microbatches, fp8 in the GELU MLP and in ``linear_tee``.
 """
 from __future__ import annotations
@@ -21,8 +23,8 @@ from .. import ops
 class Fp8Linear(nn.Linear):
     """``nn.Linear`` whose forward is ``ops.linear(x, weight, bias, fp8=self.fp8_mode)``: K17 where
     ``ops.fp8_linear_supported`` holds (HIP bf16 tensors, feature counts multiples of 16, gradients
-    enabled), the bf16 path of ``ops.linear`` otherwise.  ``fp8_mode``: ``True``, or ``"wgrad"`` for the
-    weight gradient on K17W too."""
+    enabled), the bf16 path of ``ops.linear`` otherwise.  ``fp8_mode``: ``True``, ``"wgrad"`` for the
+    weight gradient on K17W too, or ``"mx"`` for MX block scaling on K17X (feature counts multiples of 32)."""
 
     fp8_mode = True
 
@@ -30,22 +32,27 @@ class Fp8Linear(nn.Linear):
         return ops.linear(x, self.weight, self.bias, fp8=self.fp8_mode)
 
 
-def use_fp8_linears(model: nn.Module, skip: Sequence[str] = ("lm_head", "decoder"), wgrad: bool = False) -> int:
+def use_fp8_linears(model: nn.Module, skip: Sequence[str] = ("lm_head", "decoder"), wgrad: bool = False,
+                    mx: bool = False) -> int:
     """Re-class every eligible plain ``nn.Linear`` of ``model`` to :class:`Fp8Linear` in place (the module
     objects, their parameters and hooks stay) and return how many were converted.  Eligible: in- and
     out-features multiples of 16 and a weight that is not tied to an ``nn.Embedding``; a module whose
     qualified name contains one of ``skip`` is left alone (output heads keep bf16 logits).  Tensor-parallel
     replacements are not ``nn.Linear`` and are untouched.  ``wgrad`` sets ``fp8_mode = "wgrad"`` on the
-    converted modules."""
+    converted modules; ``mx`` sets ``fp8_mode = "mx"`` and asks for feature counts that are multiples of 32.
+    The two exclude each other (there is no MX weight gradient)."""
+    if wgrad and mx:
+        raise ValueError("use_fp8_linears: wgrad and mx cannot be combined")
+    mult = 32 if mx else 16
     tied = {id(m.weight) for m in model.modules() if isinstance(m, nn.Embedding)}
     n = 0
     for name, m in model.named_modules():
         if type(m) is not nn.Linear or any(s in name for s in skip) or id(m.weight) in tied:
             continue
-        if m.in_features % 16 or m.out_features % 16:
+        if m.in_features % mult or m.out_features % mult:
             continue
         m.__class__ = Fp8Linear
-        if wgrad:
-            m.fp8_mode = "wgrad"
+        if wgrad or mx:
+            m.fp8_mode = "mx" if mx else "wgrad"
         n += 1
     return n

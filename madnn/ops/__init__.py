@@ -2325,8 +2325,9 @@ def gelu_mlp(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: 
 
 
 # --------------------------------------------------------------------------- K17 (fp8 Linear)
-# ops.linear(fp8=None) takes the fp8 path (opt-in): False, True, or "wgrad" (the weight gradient on K17W too)
-FP8_LINEAR = {"0": False, "wgrad": "wgrad"}.get(os.environ.get("MADNN_FP8_LINEAR", "0"), True)
+# ops.linear(fp8=None) takes the fp8 path (opt-in): False, True, "wgrad" (the weight gradient on K17W too) or
+# "mx" (block-scaled operands on K17X)
+FP8_LINEAR = {"0": False, "wgrad": "wgrad", "mx": "mx"}.get(os.environ.get("MADNN_FP8_LINEAR", "0"), True)
 _FP8_FMT = {"e4m3": 0, "e5m2": 1}
 
 
@@ -2452,11 +2453,109 @@ class _LinearFp8Fn(torch.autograd.Function):
         return dx, dw, db, (g if ctx.has_res else None), None
 
 
-def _fp8_linear_ok(x, weight, bias, residual) -> bool:
-    return (torch.is_grad_enabled() and fp8_linear_supported(x, weight)
+def _fp8_linear_ok(x, weight, bias, residual, supported=fp8_linear_supported) -> bool:
+    return (torch.is_grad_enabled() and supported(x, weight)
             and (bias is None or (_is_dev(bias) and bias.dtype in (torch.float32, torch.bfloat16)))
             and (residual is None or (_is_dev(residual) and residual.dtype == torch.bfloat16
                                       and residual.shape[-1] == weight.shape[0])))
+
+
+# --------------------------------------------------------------------------- K17X (MX fp8 Linear)
+def mx_quantize(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False):
+    """``(q, e, qt, et)``: the 2-D bf16 ``x`` [R, C] in the OCP MX format -- blocks of 32 along C, each with its
+    own E8M0 scale byte ``e`` [R, C / 32] (uint8, value ``2^(e - 127)``) taken from the block's amax, elements
+    cast to ``torch.float8_e4m3fn`` / ``float8_e5m2`` (``reference.mx_quantize``).  With ``transpose`` the same
+    launch also quantises ``x.t()``: ``qt`` [C, R] in blocks along R with ``et`` [C, R / 32] (its own scales, not
+    a transpose of ``q``); ``None`` otherwise.  One launch, one read of ``x``, no global amax.  ``C % 32 == 0``,
+    and ``R % 32 == 0`` with ``transpose``.  ``e`` / ``et`` are views of row-padded buffers that
+    :func:`mx_gemm` reads in place.  Plain torch on CPU tensors."""
+    if fmt not in _FP8_FMT:
+        raise ValueError(f"mx_quantize: fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
+    if x.dim() != 2:
+        raise ValueError("mx_quantize: x must be 2-D")
+    if not _is_dev(x):
+        return (*reference.mx_quantize(x, fmt), *(reference.mx_quantize(x.t(), fmt) if transpose else (None, None)))
+    q, e, qt, et = _need_native("mx_quantize").mx_quant(_fp8_rows(x), _FP8_FMT[fmt], transpose)
+    return q, e, (qt if transpose else None), (et if transpose else None)
+
+
+def _mx_scales(e: torch.Tensor, k: int) -> torch.Tensor:
+    """Scale bytes ``e`` [rows, k / 32] as K17X fetches them, one aligned 32-bit word per row and 128-byte K step:
+    ``e`` itself if its rows are 4-B aligned and padded to whole words inside its storage (what
+    :func:`mx_quantize` returns), else a copy into such a buffer.  The pad bytes may hold anything."""
+    ld = 4 * ((k + 127) // 128)
+    if (e.stride(1) == 1 and e.stride(0) % 4 == 0 and e.stride(0) >= ld and e.data_ptr() % 4 == 0
+            and e.storage_offset() + (e.shape[0] - 1) * e.stride(0) + ld <= e.untyped_storage().nbytes()):
+        return e
+    buf = e.new_empty(e.shape[0], ld)[:, :e.shape[1]]
+    return buf.copy_(e)
+
+
+def mx_gemm(a8: torch.Tensor, ea: torch.Tensor, b8: torch.Tensor, eb: torch.Tensor,
+            bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K17X: bf16 ``dq(a8, ea) @ dq(b8, eb).T (+ bias) (+ residual)`` for fp8 ``a8`` [M, K] and ``b8`` [N, K] (each
+    e4m3fn or e5m2) with uint8 E8M0 block scales ``ea`` [M, K / 32] and ``eb`` [N, K / 32]
+    (``dq(q, e)[r, k] = q[r, k] * 2^(e[r, k // 32] - 127)``), the scaling done by the MFMA; fp32 accumulation, one
+    rounding.  ``K % 32 == 0`` and ``N % 8 == 0``.  Scales from :func:`mx_quantize` are read in place, any other
+    [rows, K / 32] uint8 tensor is copied into the padded layout first.  Plain torch on CPU tensors."""
+    if ea.dtype != torch.uint8 or eb.dtype != torch.uint8 or ea.shape != (a8.shape[0], a8.shape[1] // 32) \
+            or eb.shape != (b8.shape[0], b8.shape[1] // 32):
+        raise ValueError("mx_gemm: scales must be uint8 [rows, K / 32]")
+    if not _is_dev(a8):
+        y = reference.mx_dequantize(a8, ea) @ reference.mx_dequantize(b8, eb).t()
+        y = y + bias.float() if bias is not None else y
+        return (y + residual.float() if residual is not None else y).to(torch.bfloat16)
+    k = a8.shape[1]
+    return _need_native("mx_gemm").mx_gemm(a8, _mx_scales(ea, k), b8, _mx_scales(eb, k), bias, residual)
+
+
+def mx_linear_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Whether ``linear(x, weight, fp8="mx")`` runs K17X: as :func:`fp8_linear_supported`, with in- and
+    out-features multiples of 32 (whole MX blocks in both reduction directions)."""
+    return fp8_linear_supported(x, weight) and weight.shape[0] % 32 == 0 and weight.shape[1] % 32 == 0
+
+
+class _LinearMxFn(torch.autograd.Function):
+    """y = x W^T + b (+ residual) with the forward and the data gradient on K17X, all operands MX e4m3.
+
+    Forward: x quantised in blocks along in-features (one launch), W in blocks along in-features and, by the
+    same launch, W^T in blocks along out-features; one K17X GEMM with bias and residual in its epilogue.
+    Saved: bf16 x, the out-blocked weight image and its scales.  Backward: dy quantised in blocks along
+    out-features, dx = K17X(dy8, w8t); weight, bias and residual gradients exactly as :class:`_LinearFp8Fn`
+    without ``wgrad`` (bf16 :func:`_weight_grad` on the saved x)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual):
+        k = _need_native("mx linear")
+        n = weight.shape[0]
+        x8, ex, _, _ = k.mx_quant(_fp8_rows(x), 0, False)
+        w8, ew, w8t, ewt = k.mx_quant(_fp8_rows(weight), 0, True)
+        res2 = residual.reshape(-1, n).contiguous() if residual is not None else None
+        y = k.mx_gemm(x8, ex, w8, ew, bias, res2)
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        ctx.param = weight
+        ctx.has_res = residual is not None
+        ctx.x_shape = x.shape
+        ctx.save_for_backward(x, w8t, ewt)
+        return y.view(*x.shape[:-1], n)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w8t, ewt = ctx.saved_tensors
+        db = dx = dw = None
+        if ctx.bias_dtype is not None and ctx.needs_input_grad[2]:
+            db = _out_bias_grad(g, ctx.bias_dtype)
+        g2 = g.reshape(-1, g.shape[-1])
+        if not g2.is_contiguous():
+            g2 = g2.contiguous()
+        if ctx.needs_input_grad[0]:
+            k = _need_native("mx linear")
+            g8, eg, _, _ = k.mx_quant(g2, 0, False)
+            dx = k.mx_gemm(g8, eg, w8t, ewt, None, None).view(ctx.x_shape)
+        if ctx.needs_input_grad[1]:
+            dw = _weight_grad(g2, x.reshape(-1, ctx.x_shape[-1]), ctx.param)
+        ctx.param = None
+        return dx, dw, db, (g if ctx.has_res else None)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, gelu: bool = False,
@@ -2471,16 +2570,24 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     and :func:`fp8_linear_supported` holds; in every other case the call is what it is without ``fp8``.
     ``fp8=True`` on CPU tensors runs ``reference.linear_fp8`` (the same numerics in plain torch).
     ``fp8="wgrad"`` (``MADNN_FP8_LINEAR=wgrad``) is that path with the weight gradient on the fp8 GEMM K17W
-    as well: the backward keeps the e4m3 image of ``x`` instead of ``x`` (``reference.linear_fp8(wgrad=True)``)."""
+    as well: the backward keeps the e4m3 image of ``x`` instead of ``x`` (``reference.linear_fp8(wgrad=True)``).
+    ``fp8="mx"`` (``MADNN_FP8_LINEAR=mx``) is the MX recipe instead of the per-tensor one: x, W and dy as e4m3
+    with one E8M0 scale per 32 elements along the reduction, forward and data gradient on the block-scaled GEMM
+    K17X (:class:`_LinearMxFn`) where :func:`mx_linear_supported` holds, ``reference.linear_mx`` on CPU tensors."""
     if residual is not None and residual.shape[:-1] != x.shape[:-1]:
         raise ValueError("linear: residual must have the output's shape")
     mode = FP8_LINEAR if fp8 is None else fp8
-    if mode not in (None, False, True, "wgrad"):
-        raise ValueError(f"linear: fp8 must be None, a bool or 'wgrad', not {fp8!r}")
+    if mode not in (None, False, True, "wgrad", "mx"):
+        raise ValueError(f"linear: fp8 must be None, a bool, 'wgrad' or 'mx', not {fp8!r}")
     if mode and not gelu:
         if fp8 and not _is_dev(x):
+            if mode == "mx":
+                return reference.linear_mx(x, weight, bias, residual)
             return reference.linear_fp8(x, weight, bias, residual, wgrad=mode == "wgrad")
-        if _fp8_linear_ok(x, weight, bias, residual):
+        if mode == "mx":
+            if _fp8_linear_ok(x, weight, bias, residual, mx_linear_supported):
+                return _LinearMxFn.apply(x, weight, bias, residual)
+        elif _fp8_linear_ok(x, weight, bias, residual):
             return _LinearFp8Fn.apply(x, weight, bias, residual, mode == "wgrad")
     if not torch.is_grad_enabled() or (not force_fn and (not _is_dev(x) or weight.shape[0] % 8)):
         if not torch.is_grad_enabled() and _is_dev(x) and (gelu or residual is not None) and weight.shape[0] % 8 == 0:
@@ -2503,6 +2610,7 @@ __all__ = [
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
     "fp8_quantize", "fp8_gemm", "fp8_wgrad", "fp8_linear_supported", "FP8_LINEAR",
+    "mx_quantize", "mx_gemm", "mx_linear_supported",
 ]
 
 if os.environ.get("MADNN_EAGER_LOAD", "0") == "1":

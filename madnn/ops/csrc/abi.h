@@ -384,5 +384,18 @@ int madnn_fp8_wgrad_splits(int64_t M, int64_t N, int64_t K);
 hipError_t madnn_fp8_wgrad(const void* dy8, int fmt_g, const void* x8, int fmt_x, const float* inv_g,
                            const float* inv_x, void* dw, float* ws, int splits, int64_t M, int64_t N, int64_t K,
                            int64_t ldg, int64_t ldx, hipStream_t stream);
+// MX quantiser (one launch): x bf16 [R][C] with row stride ldx -> q: fp8 [R][C] quantised in blocks of 32 along C,
+// e: E8M0 scale bytes [R][lde] (byte j of a row: block j; lde % 4 == 0, lde >= 4 ceil(C / 128), 4-B aligned; pad
+// bytes are unspecified).  qt (optional, with et / ldet likewise over R): fp8 [C][R] quantised along R.
+// C % 32 == 0, ldx % 8 == 0, 16-B aligned x / q / qt; with qt also R % 32 == 0.
+hipError_t madnn_mx_quant(const void* x, int64_t ldx, int64_t R, int64_t C, int fmt, void* q, void* e, int64_t lde,
+                          void* qt, void* et, int64_t ldet, hipStream_t stream);
+// K17X: out[M][N] (bf16) = sum_k a[m][k] 2^(ea[m][k / 32] - 127) b[n][k] 2^(eb[n][k / 32] - 127) (+ bias[N])
+// (+ res[M][N]); a / b fp8 as in madnn_fp8_gemm, ea / eb scale bytes in the layout madnn_mx_quant writes (row
+// strides ldea / ldeb >= 4 ceil(K / 128), multiples of 4, 4-B aligned; bytes of a row past K / 32 are never used).
+// K % 32 == 0, N % 8 == 0.
+hipError_t madnn_mx_gemm(const void* a, int fmt_a, const void* ea, int64_t ldea, const void* b, int fmt_b,
+                         const void* eb, int64_t ldeb, const void* bias, int bias_f32, const void* res, void* out,
+                         int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, hipStream_t stream);
 
 }  // extern "C"

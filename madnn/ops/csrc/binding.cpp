@@ -1778,6 +1778,75 @@ at::Tensor fp8_wgrad(const at::Tensor& dy8, const at::Tensor& inv_g, const at::T
 
 int64_t fp8_wgrad_splits(int64_t M, int64_t N, int64_t K) { return madnn_fp8_wgrad_splits(M, N, K); }
 
+// ---- K17X MX-scaled fp8 GEMM and its quantiser (fp8.hip) ---------------------------------------
+// row stride of a scale tensor over a reduction of k elements: whole 32-bit words of 4 block scales
+int64_t mx_scale_ld(int64_t k) { return 4 * ((k + 127) / 128); }
+
+// x: bf16 [R, C] (row stride allowed) -> (q [R, C], e [R, C / 32], qt [C, R] or empty, et [C, R / 32] or empty);
+// e and et are the leading columns of buffers with rows padded to mx_scale_ld: what mx_gemm reads in place
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> mx_quant(const at::Tensor& x, int64_t fmt, bool transpose) {
+  fp8_rows_check(x, "x", 8);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "mx_quant: x must be bf16");
+  TORCH_CHECK(fmt == 0 || fmt == 1, "mx_quant: fmt 0 (e4m3fn) or 1 (e5m2)");
+  const int64_t R = x.size(0), C = x.size(1);
+  TORCH_CHECK(R > 0 && C > 0 && C % 32 == 0 && (!transpose || R % 32 == 0),
+              "mx_quant: C % 32 == 0 (and R % 32 == 0 for the transposed image), got R=", R, " C=", C);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const auto qopt = x.options().dtype(fmt == 1 ? at::kFloat8_e5m2 : at::kFloat8_e4m3fn);
+  const auto eopt = x.options().dtype(at::kByte);
+  const int64_t lde = mx_scale_ld(C), ldet = mx_scale_ld(R);
+  at::Tensor q = at::empty({R, C}, qopt), e = at::empty({R, lde}, eopt);
+  at::Tensor qt = transpose ? at::empty({C, R}, qopt) : at::empty({0}, qopt);
+  at::Tensor et = transpose ? at::empty({C, ldet}, eopt) : at::empty({0, 0}, eopt);
+  check(madnn_mx_quant(x.data_ptr(), x.stride(0), R, C, (int)fmt, q.data_ptr(), e.data_ptr(), lde,
+                       transpose ? qt.data_ptr() : nullptr, transpose ? et.data_ptr() : nullptr, ldet, cur_stream(x)),
+        "mx_quant");
+  return {q, e.narrow(1, 0, C / 32), qt, transpose ? et.narrow(1, 0, R / 32) : et};
+}
+
+// scale bytes [rows, K / 32] that K17X can read in place: see madnn_mx_gemm; the padded row must lie in the storage
+void mx_scale_check(const at::Tensor& e, const char* name, int64_t rows, int64_t K) {
+  check_dev(e, name);
+  TORCH_CHECK(e.scalar_type() == at::kByte && e.dim() == 2 && e.size(0) == rows && e.size(1) == K / 32, "mx_gemm: ",
+              name, " must be uint8 [rows, K / 32]");
+  const int64_t ld = e.stride(0), ldmin = mx_scale_ld(K);
+  TORCH_CHECK(e.stride(1) == 1 && ld % 4 == 0 && ld >= ldmin && reinterpret_cast<uintptr_t>(e.data_ptr()) % 4 == 0 &&
+                  e.storage_offset() + (rows - 1) * ld + ldmin <= (int64_t)e.storage().nbytes(),
+              "mx_gemm: ", name, " needs 4-B aligned rows padded to whole 32-bit words (ops.mx_gemm makes them)");
+}
+
+// y [M, N] bf16 = sum_k a8[m, k] 2^(ea[m, k / 32] - 127) b8[n, k] 2^(eb[n, k / 32] - 127) (+ bias) (+ res)
+at::Tensor mx_gemm(const at::Tensor& a, const at::Tensor& ea, const at::Tensor& b, const at::Tensor& eb,
+                   const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res) {
+  fp8_rows_check(a, "a", 16);
+  fp8_rows_check(b, "b", 16);
+  const int fa = fp8_fmt(a, "a"), fb = fp8_fmt(b, "b");
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  TORCH_CHECK(b.size(1) == K && M > 0 && N > 0 && K > 0 && K % 32 == 0 && N % 8 == 0,
+              "mx_gemm: a [M, K], b [N, K] with K % 32 == 0 and N % 8 == 0, got M=", M, " N=", N, " K=", K);
+  mx_scale_check(ea, "ea", M, K);
+  mx_scale_check(eb, "eb", N, K);
+  const bool hb = bias.has_value() && bias->defined();
+  if (hb) {
+    check_dev(*bias, "bias");
+    TORCH_CHECK(bias->numel() == N && bias->is_contiguous() &&
+                    (bias->scalar_type() == at::kFloat || bias->scalar_type() == at::kBFloat16),
+                "mx_gemm: bias must be a contiguous fp32/bf16 [N]");
+  }
+  const bool hr = res.has_value() && res->defined();
+  if (hr) {
+    gemm_check(*res, "res");
+    TORCH_CHECK(res->numel() == M * N && res->size(-1) == N, "mx_gemm: residual shape");
+  }
+  at::hip::HIPGuardMasqueradingAsCUDA guard(a.device());
+  at::Tensor y = at::empty({M, N}, a.options().dtype(at::kBFloat16));
+  check(madnn_mx_gemm(a.data_ptr(), fa, ea.data_ptr(), ea.stride(0), b.data_ptr(), fb, eb.data_ptr(), eb.stride(0),
+                      hb ? bias->data_ptr() : nullptr, hb && bias->scalar_type() == at::kFloat ? 1 : 0,
+                      hr ? res->data_ptr() : nullptr, y.data_ptr(), M, N, K, a.stride(0), b.stride(0), cur_stream(a)),
+        "mx_gemm");
+  return y;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(madnn, m) {
@@ -1785,6 +1854,8 @@ TORCH_LIBRARY(madnn, m) {
   m.def("fp8_gemm(Tensor a, Tensor inv_a, Tensor b, Tensor inv_b, Tensor? bias, Tensor? res) -> Tensor");
   m.def("fp8_wgrad(Tensor dy8, Tensor inv_g, Tensor x8, Tensor inv_x, Tensor? out, int splits) -> Tensor");
   m.def("fp8_wgrad_splits(int M, int N, int K) -> int", &fp8_wgrad_splits);
+  m.def("mx_quant(Tensor x, int fmt, bool transpose) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("mx_gemm(Tensor a, Tensor ea, Tensor b, Tensor eb, Tensor? bias, Tensor? res) -> Tensor");
   m.def("hwq_batch(Tensor kinds, Tensor msgs, Tensor(a!) a, Tensor(b!) b, int epoch, int timeout_us, Tensor(c!) ok, "
         "Tensor ok_index) -> ()");
   m.def("hwq_spin(Tensor like, int spin_us) -> ()");
@@ -1962,6 +2033,8 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("fp8_quant", fp8_quant);
   m.impl("fp8_gemm", fp8_gemm);
   m.impl("fp8_wgrad", fp8_wgrad);
+  m.impl("mx_quant", mx_quant);
+  m.impl("mx_gemm", mx_gemm);
   m.impl("conv3x3_fwd", conv3x3_fwd);
   m.impl("conv3x3_fwd_s2", conv3x3_fwd_s2);
   m.impl("conv3x3_wgrad", conv3x3_wgrad);

@@ -1,6 +1,7 @@
 // K17 -- fp8 GEMM on v_mfma_f32_32x32x64_f8f6f4 for gfx950, and the per-tensor quantiser that feeds it:
 // the forward and the data gradient of an opt-in FP8 Linear (ops.linear(fp8=True), madnn.nn.Fp8Linear).
-// K17W, the weight gradient of that Linear on the same MFMA (ops.linear(fp8="wgrad")), has its own header below.
+// K17W, the weight gradient of that Linear on the same MFMA (ops.linear(fp8="wgrad")), has its own header below,
+// and so have K17X, the MX block-scaled GEMM (ops.linear(fp8="mx")), and its one-pass quantiser.
 //
 // Formats: OCP e4m3fn (activations, weights) and e5m2 (output gradients), bit for bit torch's
 // float8_e4m3fn / float8_e5m2.  Scaling is per tensor and current: scale = 2^floor(log2(FMAX / amax)) of the
@@ -607,6 +608,350 @@ hipError_t launch_wgrad(const WArgs& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------- MX quantiser, K17X
+// OCP MX block scaling: every 32 consecutive elements along the reduction dimension of the GEMM that consumes
+// an image share one E8M0 scale byte e (value 2^(e - 127)); the elements are e4m3fn or e5m2.
+//   e = clamp(floor(log2 amax_block) + 127 - EMAX, 0, 254), EMAX = 8 (e4m3) / 15 (e5m2); all-zero block: e = 127.
+// floor(log2 amax) + 127 is the exponent field E of the block's bf16 amax (the max is taken on the bit patterns,
+// as in the per-tensor quantiser), so e = max(E - EMAX, 0): no division, no log; a subnormal amax has E = 0 and
+// meets the clamp at 0; a finite bf16 has E <= 254, so e <= 246 and the upper clamp never binds.
+// Elements: x * 2^(127 - e).  That factor has the fp32 exponent field 254 - e, in [8, 254] for every e the
+// quantiser forms: always a normal fp32 number, and a power of two, so the product is exact in fp32 (|x| <
+// 2^(e - 127 + EMAX + 1) keeps it below 2^(EMAX + 1); a bf16 subnormal times 2^127 is a normal fp32).  amax / X
+// lies in [2^EMAX, 2^(EMAX + 1)) and FMAX is 1.75 * 2^EMAX, so the product is clamped to +-FMAX explicitly and
+// only then cast (v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32, round to nearest even): the result does not depend on
+// what the cast does on overflow.  Non-finite inputs: unspecified.
+//
+// Quantiser: ONE launch, one read of x, no amax pass (a block's scale is a function of that block alone), no
+// atomics, no host sync.  A 256-thread workgroup takes a 64 x 64 bf16 tile.  Row image q [R][C] (blocks along
+// C): lane (row tid / 4, columns 16 (tid & 3) .. + 15) loads 32 B, the two lanes of a block exchange their amax
+// with one DPP shuffle, and each casts and stores 16 B; one lane in four stores the tile's two scale bytes of
+// its row as one 16-bit word.  Transposed image qt [C][R] (blocks along R, R % 32 == 0) -- a second quantisation
+// with its own scales, not a transpose of q: the data gradient needs W^T blocked along out-features.  The raw
+// bf16 tile goes through LDS once (8 KiB; 16-B chunk c of row r at slot c ^ 2 (r >> 4): a wave's 16-bit column
+// reads then touch 32 different banks, two lanes per word); lane (column tid / 4, rows 16 (tid & 3) .. + 15)
+// gathers its 16 values, the lane pair of a block shuffles the amax, and 16 B leave down the column: 4 lanes
+// write 64 contiguous bytes of qt.
+//
+// Scale layout (what K17X reads): uint8 [rows][ld], k-contiguous, ld % 4 == 0, ld >= 4 ceil(K / 128), base 4-B
+// aligned -- so the 4 scale bytes of a row's 128-byte K step are ONE aligned 32-bit word, word t of the row.
+// Bytes of a row past K / 32 need not hold anything in particular: K17X replaces them (below).  The quantiser
+// writes 127 into the pad bytes its 16-bit stores cover and leaves the rest.
+//
+// K17X: C[M][N] (bf16) = sum_k (A[m][k] 2^(ea[m][k / 32] - 127)) (B[n][k] 2^(eb[n][k / 32] - 127)) (+ bias)
+// (+ residual) on v_mfma_scale_f32_32x32x64_f8f6f4.  Geometry, data ring, swizzle, fragment reads and epilogue
+// are K17's (its header above); the epilogue has no scale factor.  New are the k order of a fragment and the
+// scale path.
+// Which k a register byte is: the hardware's k index of the 32 operand bytes of lane l (row l & 31, half
+// h = l >> 5) is 16 h .. + 15 for register bytes 0..15 and 32 + 16 h .. + 15 for bytes 16..31, and the scale of
+// hardware k block j (k 32 j .. + 31) of a row is taken from the lane of that row in half j.  K17 need not care
+// (both operands use one map, any bijection of k gives the same sum); here a block must meet its scale, so
+// frag_mx reads 16-B chunks 4 s + h and 4 s + 2 + h of the row for MFMA s (K17: 4 s + 2 h and the next) -- still
+// two ds_read_b128 with a chunk index that is uniform per 32-lane half, so K17's bank argument holds unchanged.
+// tests/test_mx_gpu.py::test_scale_routing_exact (independent scales per row and block) is the proof.
+// Scale path: lane (row, half h) supplies the scale of block h of the MFMA's 64 k in a VGPR; op_sel picks the
+// byte.  MFMA s (0, 1) of a K step needs byte 2 s + h of the row's scale word.  op_sel is an immediate, so each
+// word is permuted once per K step
+// (v_perm_b32 with a per-lane selector) to hold byte (l >> 5) in byte 0 and byte 2 + (l >> 5) in byte 3, and the
+// two MFMAs select bytes 0 and 3 (op_sel 0 and op_sel + op_sel_hi both set).
+// The words travel through the same ring as the data: LDS holds 2 more KiB per stage (A words [256], B words
+// [256]), wave w streams ONE extra piece per stage with glds4 -- lane l the word of row 64 (w & 3) + l of its
+// image -- issued after its 8 data pieces.  Chosen over per-lane global loads because those would sit in the
+// MFMA loop as 6 dependent VMEM loads per step that hipcc counts in vmcnt and would drain together with the
+// uncounted DMA; through the ring they cost 6 conflict-free ds_read_b32 (32 consecutive words, both lane halves
+// the same address).  Counted wait: a wave now has 9 loads per stage in flight, so K tile t is complete at
+// vmcnt(9) after the 9 of K tile t + 1 were issued (loads retire in order); the RAW / WAR argument is K17's
+// unchanged -- the barrier after the wait publishes stage t & 1 (data and words), lgkmcnt(0) + barrier after the
+// last fragment and word read opens it for K tile t + 2 -- because the words live and die with their stage.
+// Ragged shapes: any M, N % 8 == 0, K % 32 == 0 (K need not be a multiple of 128).  Data lanes outside the
+// operand read the zero block as in K17.  A scale lane whose row is outside reads g_one_word (four bytes of 127)
+// and never forms an address past the last row; inside, word t < ceil(K / 128) is within the row by the layout
+// contract.  Bytes of the last word at or past K / 32 are replaced by 127 with one v_bfi per word (a uniform
+// mask): a zero fragment times 2^(255 - 127) would be NaN, so no pad byte, next row or foreign byte reaches a
+// result.
+constexpr int kXScale = 2 * kT * 4;        // scale words of one stage: A [256], B [256]
+constexpr int kXLds = kLds + 2 * kXScale;  // 132 KiB of the CU's 160
+
+__device__ unsigned g_one_word = 0x7f7f7f7fu;  // what an out-of-range scale lane reads: 2^0 four times
+
+// E8M0 byte of a block from the bit pattern of its bf16 amax (sign bit clear)
+template <int FMT>
+__device__ __forceinline__ unsigned mx_scale_byte(unsigned amax_bits) {
+  constexpr int EMAX = FMT == kE5M2 ? 15 : 8;
+  const int e = (int)(amax_bits >> 7) - EMAX;
+  return amax_bits == 0 ? 127u : (unsigned)(e < 0 ? 0 : e);
+}
+
+__device__ __forceinline__ unsigned amax_word(unsigned m, unsigned w) {
+  const unsigned lo = w & 0x7fffu, hi = (w >> 16) & 0x7fffu;
+  m = m > lo ? m : lo;
+  return m > hi ? m : hi;
+}
+
+template <int FMT>
+__device__ __forceinline__ float mx_fit(float x, float f) {
+  constexpr float FMAX = FMT == kE5M2 ? 57344.f : 448.f;
+  return fminf(fmaxf(x * f, -FMAX), FMAX);
+}
+
+// four bf16 in two words -> four fp8 bytes of a block with factor f = 2^(127 - e)
+template <int FMT>
+__device__ __forceinline__ unsigned mx_cvt4(unsigned a, unsigned b, float f) {
+  return cvt4<FMT>(mx_fit<FMT>(bf16_lo(a), f), mx_fit<FMT>(bf16_hi(a), f), mx_fit<FMT>(bf16_lo(b), f),
+                   mx_fit<FMT>(bf16_hi(b), f));
+}
+
+template <int FMT, bool TR>
+__global__ __launch_bounds__(kQThreads) void mx_quant_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t R,
+                                                             int C, uint8_t* __restrict__ q, uint8_t* __restrict__ e,
+                                                             int64_t lde, uint8_t* __restrict__ qt,
+                                                             uint8_t* __restrict__ et, int64_t ldet) {
+  __shared__ __attribute__((aligned(16))) uint16_t tile[kQTile * kQTile];
+  const int ctiles = (C + kQTile - 1) / kQTile;
+  const int64_t rt = blockIdx.x / ctiles;
+  const int ct = (int)(blockIdx.x - rt * ctiles);
+  const int tid = threadIdx.x, lr = tid >> 2, lq = tid & 3;
+  const int64_t r = rt * kQTile + lr;
+  const int c = ct * kQTile + 16 * lq;
+  const bool in = r < R && c < C;  // C % 32 == 0: a block is inside or outside as a whole
+  u32x4 a = u32x4{0u, 0u, 0u, 0u}, b = a;
+  if (in) {
+    a = *reinterpret_cast<const u32x4*>(x + r * ldx + c);
+    b = *reinterpret_cast<const u32x4*>(x + r * ldx + c + 8);
+  }
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m = amax_word(amax_word(m, a[i]), b[i]);
+  const unsigned mo = (unsigned)__shfl_xor((int)m, 1, kWave);  // the block's other half
+  const unsigned eb = mx_scale_byte<FMT>(m > mo ? m : mo);
+  const unsigned eb2 = (unsigned)__shfl_xor((int)eb, 2, kWave);  // the row's other block of this tile
+  if (in) {
+    const float f = __uint_as_float((254u - eb) << 23);
+    *reinterpret_cast<u32x4*>(q + r * C + c) = u32x4{mx_cvt4<FMT>(a[0], a[1], f), mx_cvt4<FMT>(a[2], a[3], f),
+                                                     mx_cvt4<FMT>(b[0], b[1], f), mx_cvt4<FMT>(b[2], b[3], f)};
+    // a block outside C has amax 0: its byte (127) lands in the row's padding, which lde covers
+    if (lq == 0) *reinterpret_cast<uint16_t*>(e + r * lde + 2 * ct) = (uint16_t)(eb | (eb2 << 8));
+  }
+  if constexpr (TR) {
+    u32x4* const trow = reinterpret_cast<u32x4*>(tile + lr * kQTile);
+    const int fw = 2 * (lr >> 4);
+    trow[(2 * lq) ^ fw] = a;
+    trow[(2 * lq + 1) ^ fw] = b;
+    __syncthreads();
+    const int tc = tid >> 2, tg = tid & 3;
+    const int64_t r0 = rt * kQTile + 16 * tg;
+    const int cc = ct * kQTile + tc;
+    const uint16_t* const col = tile + 16 * tg * kQTile + 8 * ((tc >> 3) ^ (2 * tg)) + (tc & 7);
+    unsigned w[8];  // rows 2 j, 2 j + 1 of the lane's 16 as a bf16 pair
+    unsigned mt = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      w[j] = (unsigned)col[2 * j * kQTile] | ((unsigned)col[(2 * j + 1) * kQTile] << 16);
+      mt = amax_word(mt, w[j]);
+    }
+    const unsigned mto = (unsigned)__shfl_xor((int)mt, 1, kWave);
+    const unsigned ebt = mx_scale_byte<FMT>(mt > mto ? mt : mto);
+    const unsigned ebt2 = (unsigned)__shfl_xor((int)ebt, 2, kWave);
+    if (cc < C && r0 < R) {  // R % 32 == 0: whole blocks
+      const float f = __uint_as_float((254u - ebt) << 23);
+      *reinterpret_cast<u32x4*>(qt + (int64_t)cc * R + r0) = u32x4{
+          mx_cvt4<FMT>(w[0], w[1], f), mx_cvt4<FMT>(w[2], w[3], f), mx_cvt4<FMT>(w[4], w[5], f), mx_cvt4<FMT>(w[6], w[7], f)};
+      if (tg == 0) *reinterpret_cast<uint16_t*>(et + (int64_t)cc * ldet + 2 * rt) = (uint16_t)(ebt | (ebt2 << 8));
+    }
+  }
+}
+
+struct XArgs {
+  const uint8_t* a;
+  const uint8_t* b;
+  const uint8_t* ea;     // scale bytes [M][ldea] (header: Scale layout)
+  const uint8_t* eb;     // [N][ldeb]
+  uint16_t* out;
+  const uint16_t* res;   // [M][N] bf16 or null
+  const void* bias;      // [N] fp32 (bias_f32) or bf16, or null
+  int64_t lda, ldb, ldea, ldeb;
+  int64_t M, N, K;
+  int m_tiles, n_tiles;
+  int bias_f32;
+};
+
+// the 32 operand bytes of MFMA step s that lane half hh holds of row `row`: chunks 4s + hh and 4s + 2 + hh (header)
+__device__ __forceinline__ i32x8 frag_mx(const uint8_t* img, int row, int s, int hh) {
+  const int f = swzf(row);
+  const u32x4 lo = *reinterpret_cast<const u32x4*>(img + row * kBK + 16 * ((4 * s + hh) ^ f));
+  const u32x4 hi = *reinterpret_cast<const u32x4*>(img + row * kBK + 16 * ((4 * s + 2 + hh) ^ f));
+  return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
+
+// OP: which byte of the lane's scale registers both operands use (0 or 3, header)
+template <int FA, int FB, int OP>
+__device__ __forceinline__ f32x16 mfmax(const i32x8& nfrag, const i32x8& mfrag, const f32x16& c, unsigned en,
+                                        unsigned em) {
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(nfrag, mfrag, c, FB, FA, OP, (int)en, OP, (int)em);
+}
+
+template <int FA, int FB>
+__global__ __launch_bounds__(kThreads) void mx_gemm_kernel(const XArgs p) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[kXLds];
+  const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, l32 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 2, wc = wave & 3;
+
+  const int wid = xcd_group_id(blockIdx.x, gridDim.x);
+  const int nt = wid % p.n_tiles, mt = wid / p.n_tiles;
+  const int64_t m0 = (int64_t)mt * kT, n0 = (int64_t)nt * kT;
+  const int64_t K = p.K;
+  const int nk = (int)((K + kBK - 1) / kBK);
+  const int kblocks = (int)(K >> 5);
+
+  // DMA sources as K17: waves 0..3 stream the A image and A's scale words, 4..7 B's
+  const bool is_a = wave < 4;
+  const uint8_t* const op = is_a ? p.a : p.b;
+  const int64_t ld = is_a ? p.lda : p.ldb;
+  const int64_t x0 = is_a ? m0 : n0, lim = is_a ? p.M : p.N;
+  const uint8_t* src[kPieces];
+#pragma unroll
+  for (int e = 0; e < kPieces; ++e) {
+    const int row = 64 * (wave & 3) + 8 * e + (lane >> 3);
+    const int kc = 16 * ((lane & 7) ^ swzf(row));
+    src[e] = x0 + row < lim ? op + (x0 + row) * ld + kc : nullptr;
+  }
+  const int kc_even = 16 * ((lane & 7) ^ swzf(lane >> 3)), kc_odd = 16 * ((lane & 7) ^ swzf(8 + (lane >> 3)));
+  uint8_t* const dma_dst = smem + (is_a ? 0 : kImage) + (wave & 3) * (kPieces * 1024);
+  // scale piece: lane l the words of row 64 (wave & 3) + l, or the constant word for a row outside
+  const int64_t erow = x0 + 64 * (wave & 3) + lane;
+  const uint8_t* const esrc = erow < lim ? (is_a ? p.ea + erow * p.ldea : p.eb + erow * p.ldeb) : nullptr;
+  uint8_t* const edst = smem + kLds + (is_a ? 0 : kT * 4) + (wave & 3) * 256;
+
+  auto stage = [&](int t) {
+    const int64_t kb = (int64_t)t * kBK;
+#pragma unroll
+    for (int e = 0; e < kPieces; ++e) {
+      const bool in = src[e] != nullptr && kb + ((e & 1) ? kc_odd : kc_even) < K;
+      const void* s = in ? (const void*)(src[e] + kb) : (const void*)g_zero16;
+      glds16(s, (lds_void*)(dma_dst + (t & 1) * kStage + e * 1024));
+    }
+    const void* s = esrc != nullptr ? (const void*)(esrc + 4 * t) : (const void*)&g_one_word;
+    glds4(s, (lds_void*)(edst + (t & 1) * kXScale));
+  };
+
+  // per-lane v_perm selector: byte 0 <- byte hh, byte 3 <- byte 2 + hh, bytes 1 and 2 <- 0 (header)
+  const unsigned sel = (unsigned)hh | 0x000c0c00u | ((unsigned)(2 + hh) << 24);
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = zero16();
+
+  stage(0);
+  for (int t = 0; t < nk; ++t) {
+    if (t + 1 < nk) {
+      stage(t + 1);
+      wait_vmcnt<kPieces + 1>();  // K tile t's pieces: all but the 9 just issued
+    } else {
+      wait_vmcnt<0>();
+    }
+    barrier();
+    const uint8_t* sa = smem + (t & 1) * kStage;
+    const uint8_t* sb = sa + kImage;
+    const unsigned* se = reinterpret_cast<const unsigned*>(smem + kLds + (t & 1) * kXScale);
+    // bytes of this step's words that are scales of the operand; the others become 127
+    const int nb = kblocks - 4 * t;
+    const unsigned msk = nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u;
+    auto word = [&](int row) {
+      const unsigned w = (se[row] & msk) | (0x7f7f7f7fu & ~msk);
+      return __builtin_amdgcn_perm(w, w, sel);
+    };
+    unsigned en[2], em[4];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) en[b] = word(kT + wc * 64 + 32 * b + l32);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) em[a] = word(wr * 128 + 32 * a + l32);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      i32x8 nf[2], mf_[4];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) nf[b] = frag_mx(sb, wc * 64 + 32 * b + l32, s, hh);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) mf_[a] = frag_mx(sa, wr * 128 + 32 * a + l32, s, hh);
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+          acc[a][b] = s == 0 ? mfmax<FA, FB, 0>(nf[b], mf_[a], acc[a][b], en[b], em[a])
+                             : mfmax<FA, FB, 3>(nf[b], mf_[a], acc[a][b], en[b], em[a]);
+    }
+    wait_lgkmcnt0();  // this stage's last fragment and word reads, before the barrier that opens it for K tile t + 2
+    barrier();
+  }
+
+  // ---- epilogue: K17's, without a scale factor
+  char* ot = reinterpret_cast<char*>(smem);
+  const int c = tid & 31, rr = tid >> 5;
+  const int64_t ng = n0 + 8 * c;
+  float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (p.bias != nullptr && ng < p.N) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      bv[j] = p.bias_f32 ? static_cast<const float*>(p.bias)[ng + j]
+                         : bf16_to_f32(static_cast<const uint16_t*>(p.bias)[ng + j]);
+  }
+#pragma unroll 1
+  for (int half = 0; half < 2; ++half) {
+    if (wr == half) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int ml = 32 * a + l32, ch = wc * 16 + 8 * b + 2 * g + hh;
+            const f32x16& v = acc[a][b];
+            *reinterpret_cast<f32x4*>(ot + ml * 1024 + 16 * (ch ^ (ml & 15))) =
+                f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+          }
+    }
+    __syncthreads();
+    if (ng < p.N) {
+#pragma unroll 2
+      for (int i = 0; i < 8; ++i) {
+        const int ml = rr + 16 * i;
+        const int64_t mg = m0 + 128 * half + ml;
+        if (mg >= p.M) break;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(ot + ml * 1024 + 16 * ((2 * c) ^ (ml & 15)));
+        const f32x4 hi = *reinterpret_cast<const f32x4*>(ot + ml * 1024 + 16 * ((2 * c + 1) ^ (ml & 15)));
+        float v[8] = {lo[0] + bv[0], lo[1] + bv[1], lo[2] + bv[2], lo[3] + bv[3],
+                      hi[0] + bv[4], hi[1] + bv[5], hi[2] + bv[6], hi[3] + bv[7]};
+        if (p.res != nullptr) {
+          float rv[8];
+          load8<kBF16>(p.res, mg * p.N + ng, rv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] += rv[j];
+        }
+        store8<kBF16>(p.out, mg * p.N + ng, v);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int FA, int FB>
+hipError_t launch_mx_gemm(const XArgs& p, int64_t grid, hipStream_t s) {
+  hipLaunchKernelGGL((mx_gemm_kernel<FA, FB>), dim3((unsigned)grid), dim3(kThreads), 0, s, p);
+  return hipGetLastError();
+}
+
+template <int FMT>
+hipError_t launch_mx_quant(const uint16_t* x, int64_t ldx, int64_t R, int C, uint8_t* q, uint8_t* e, int64_t lde,
+                           uint8_t* qt, uint8_t* et, int64_t ldet, unsigned tiles, hipStream_t s) {
+  if (qt != nullptr)
+    hipLaunchKernelGGL((mx_quant_kernel<FMT, true>), dim3(tiles), dim3(kQThreads), 0, s, x, ldx, R, C, q, e, lde, qt, et, ldet);
+  else
+    hipLaunchKernelGGL((mx_quant_kernel<FMT, false>), dim3(tiles), dim3(kQThreads), 0, s, x, ldx, R, C, q, e, lde, qt, et, ldet);
+  return hipGetLastError();
+}
+
 }  // namespace fp8
 }  // namespace madnn
 
@@ -667,6 +1012,62 @@ extern "C" hipError_t madnn_fp8_gemm(const void* a, int fmt_a, const void* b, in
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   if (fmt_a == 0) return fmt_b == 0 ? fp8::launch_gemm<0, 0>(p, grid, stream) : fp8::launch_gemm<0, 1>(p, grid, stream);
   return fmt_b == 0 ? fp8::launch_gemm<1, 0>(p, grid, stream) : fp8::launch_gemm<1, 1>(p, grid, stream);
+}
+
+extern "C" hipError_t madnn_mx_quant(const void* x, int64_t ldx, int64_t R, int64_t C, int fmt, void* q, void* e,
+                                     int64_t lde, void* qt, void* et, int64_t ldet, hipStream_t stream) {
+  if (R <= 0 || C <= 0 || C % 32 || ldx % 8 || ldx < C || C > 0x7fffffff || (fmt != 0 && fmt != 1))
+    return hipErrorInvalidValue;
+  if (x == nullptr || q == nullptr || e == nullptr || lde % 4 || lde < 4 * ((C + 127) / 128)) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(qt)) % 16 ||
+      (reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(et)) % 4)
+    return hipErrorInvalidValue;
+  if (qt != nullptr && (R % 32 || et == nullptr || ldet % 4 || ldet < 4 * ((R + 127) / 128))) return hipErrorInvalidValue;
+  const int64_t tiles = ((R + fp8::kQTile - 1) / fp8::kQTile) * ((C + fp8::kQTile - 1) / fp8::kQTile);
+  if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+  const uint16_t* xp = static_cast<const uint16_t*>(x);
+  uint8_t* qp = static_cast<uint8_t*>(q);
+  uint8_t* ep = static_cast<uint8_t*>(e);
+  uint8_t* qtp = static_cast<uint8_t*>(qt);
+  uint8_t* etp = static_cast<uint8_t*>(et);
+  if (fmt == fp8::kE5M2)
+    return fp8::launch_mx_quant<1>(xp, ldx, R, (int)C, qp, ep, lde, qtp, etp, ldet, (unsigned)tiles, stream);
+  return fp8::launch_mx_quant<0>(xp, ldx, R, (int)C, qp, ep, lde, qtp, etp, ldet, (unsigned)tiles, stream);
+}
+
+extern "C" hipError_t madnn_mx_gemm(const void* a, int fmt_a, const void* ea, int64_t ldea, const void* b, int fmt_b,
+                                    const void* eb, int64_t ldeb, const void* bias, int bias_f32, const void* res,
+                                    void* out, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                                    hipStream_t stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 || N % 8 || lda % 16 || ldb % 16 || lda < K || ldb < K)
+    return hipErrorInvalidValue;
+  if ((fmt_a != 0 && fmt_a != 1) || (fmt_b != 0 && fmt_b != 1)) return hipErrorInvalidValue;
+  const int64_t ldmin = 4 * ((K + fp8::kBK - 1) / fp8::kBK);  // whole scale words per row
+  if (ea == nullptr || eb == nullptr || ldea % 4 || ldeb % 4 || ldea < ldmin || ldeb < ldmin ||
+      (reinterpret_cast<uintptr_t>(ea) | reinterpret_cast<uintptr_t>(eb)) % 4)
+    return hipErrorInvalidValue;
+  fp8::XArgs p;
+  p.a = static_cast<const uint8_t*>(a);
+  p.b = static_cast<const uint8_t*>(b);
+  p.ea = static_cast<const uint8_t*>(ea);
+  p.eb = static_cast<const uint8_t*>(eb);
+  p.out = static_cast<uint16_t*>(out);
+  p.res = static_cast<const uint16_t*>(res);
+  p.bias = bias;
+  p.lda = lda;
+  p.ldb = ldb;
+  p.ldea = ldea;
+  p.ldeb = ldeb;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.m_tiles = (int)((M + fp8::kT - 1) / fp8::kT);
+  p.n_tiles = (int)((N + fp8::kT - 1) / fp8::kT);
+  p.bias_f32 = bias_f32;
+  const int64_t grid = (int64_t)p.m_tiles * p.n_tiles;
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  if (fmt_a == 0) return fmt_b == 0 ? fp8::launch_mx_gemm<0, 0>(p, grid, stream) : fp8::launch_mx_gemm<0, 1>(p, grid, stream);
+  return fmt_b == 0 ? fp8::launch_mx_gemm<1, 0>(p, grid, stream) : fp8::launch_mx_gemm<1, 1>(p, grid, stream);
 }
 
 // Workgroups per output tile for K17W: 256 CUs, one 128-KiB-LDS workgroup per CU.  Model, as madnn_wgrad_splits:

@@ -394,3 +394,66 @@ def linear_fp8(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = Non
     uses the unquantised tensors -- or, with ``wgrad`` (``ops.linear(fp8="wgrad")``, K17W), the same two
     dequantised images: ``dW = (dy8 / sg)^T @ (x8 / sx)``, accumulated likewise and rounded once."""
     return _LinearFp8.apply(x, w, b, residual, wgrad)
+
+
+# --------------------------------------------------------------------------- K17X (MX fp8 Linear)
+MX_BLOCK = 32
+MX_EMAX = {"e4m3": 8, "e5m2": 15}   # exponent of the format's largest binade
+
+
+def mx_quantize(x: torch.Tensor, fmt: str = "e4m3"):
+    """``(q, e)``: OCP MX quantisation of ``x`` in blocks of 32 along its last dimension (a multiple of 32).
+    ``e`` (uint8, last dimension / 32) is the E8M0 scale ``clamp(floor(log2 amax_block) + 127 - emax, 0, 254)``,
+    127 for an all-zero block; ``q`` is ``x * 2^(127 - e)`` (exact), clamped to the format's +-FMAX and cast with
+    round-to-nearest-even.  ``x ~ q * 2^(e - 127)`` (:func:`mx_dequantize`)."""
+    dtype, fmax, _ = FP8_FORMATS[fmt]
+    xd = x.detach()
+    xf = xd.to(torch.float32) if xd.dtype in (torch.bfloat16, torch.float16) else xd
+    xb = xf.reshape(*xf.shape[:-1], xf.shape[-1] // MX_BLOCK, MX_BLOCK)
+    amax = xb.abs().amax(-1)
+    _, ea = torch.frexp(amax)                      # amax = m 2^ea, m in [0.5, 1): floor(log2 amax) = ea - 1
+    e = (ea.to(torch.int32) - 1 + 127 - MX_EMAX[fmt]).clamp(0, 254)
+    e = torch.where(amax == 0, torch.full_like(e, 127), e)
+    q = (xb * torch.exp2((127 - e).to(xb.dtype)).unsqueeze(-1)).clamp(-fmax, fmax).reshape(xf.shape).to(dtype)
+    return q, e.to(torch.uint8)
+
+
+def mx_dequantize(q: torch.Tensor, e: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """``q * 2^(e - 127)`` block by block along the last dimension, in ``dtype``."""
+    s = torch.exp2(e.to(dtype) - 127).repeat_interleave(MX_BLOCK, -1)
+    return q.to(dtype) * s
+
+
+class _LinearMx(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, residual):
+        acc = torch.float32 if x.dtype in (torch.bfloat16, torch.float16) else x.dtype
+        y = mx_dequantize(*mx_quantize(x, "e4m3"), acc) @ mx_dequantize(*mx_quantize(w, "e4m3"), acc).t()
+        if b is not None:
+            y = y + b.to(acc)
+        if residual is not None:
+            y = y + residual.to(acc)
+        # the data gradient reduces over out-features: W^T quantised anew in blocks along them
+        ctx.save_for_backward(x, mx_dequantize(*mx_quantize(w.t(), "e4m3"), acc))
+        ctx.meta = (acc, x.dtype, w.dtype, b.dtype if b is not None else None, residual is not None)
+        return y.to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wtd = ctx.saved_tensors
+        acc, xdt, wdt, bdt, has_res = ctx.meta
+        dx = (mx_dequantize(*mx_quantize(g, "e4m3"), acc) @ wtd.t()).to(xdt)
+        g2, x2 = g.reshape(-1, g.shape[-1]).to(acc), x.reshape(-1, x.shape[-1]).to(acc)
+        dw = (g2.t() @ x2).to(wdt)
+        db = g2.sum(0).to(bdt) if bdt is not None else None
+        return dx, dw, db, (g if has_res else None)
+
+
+def linear_mx(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
+              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The MX FP8 Linear of ``ops.linear(fp8="mx")`` in plain torch, on any device and in any float dtype: the
+    forward multiplies the dequantised block-scaled e4m3 images of ``x`` and ``w`` (blocks of 32 along
+    in-features), adds bias and residual and rounds once; the data gradient multiplies the dequantised e4m3
+    image of the output gradient with that of ``w`` RE-QUANTISED in blocks along out-features (its reduction);
+    weight, bias and residual gradients use the unquantised tensors.  Feature counts are multiples of 32."""
+    return _LinearMx.apply(x, w, b, residual)
