@@ -11,6 +11,10 @@ The MX side (``fp8="mx"``): the one-pass block quantiser against the three-launc
 second image) and dy, K17X against K17 on images made beforehand, and the MX forward and data gradient end to end
 against the per-tensor ones and against bf16; ``k17_spread`` is K17's own max / min over the rounds, the
 run-to-run spread a K17X / K17 ratio has to be read against.
+The MX weight gradient (``fp8="mx_wgrad"``): K17XW on token-blocked images made beforehand against the bf16 weight
+gradient and against K17W (the same data bytes plus 1/32 for the scales; ``k17w_spread`` as above), the quantiser
+launches that also write the token-blocked image against the plain MX ones, and ``mx_wgrad_over_mx``, the sum of
+the pieces in which one forward + backward of the two modes differs.
 ``--out`` also writes the whole record as one JSON file."""
 import argparse
 import json
@@ -53,8 +57,10 @@ def measure(name, M, K, N, reps, rounds):
     mx8, mex, _, _ = k.mx_quant(x, 0, False)
     mw8, mew, mw8t, mewt = k.mx_quant(w, 0, True)
     mg8, meg, _, _ = k.mx_quant(dy, 0, False)
+    _, _, mx8c, mexc = k.mx_quant_cols(x, 0)
+    _, _, mg8c, megc = k.mx_quant_cols(dy, 0)
 
-    dw8, dw16 = torch.empty_like(w), torch.empty_like(w)
+    dw8, dw16, dwx = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
 
     def fp8_fwd():
         a8, _, sa = k.fp8_quant(x, 0, False)
@@ -88,6 +94,8 @@ def measure(name, M, K, N, reps, rounds):
         "k17x_fwd": lambda: k.mx_gemm(mx8, mex, mw8, mew, None, None),
         "k17x_dgrad": lambda: k.mx_gemm(mg8, meg, mw8t, mewt, None, None),
         "mx_fwd": mx_fwd, "mx_dgrad": mx_dgrad,
+        "mx_quant_cols_x": lambda: k.mx_quant_cols(x, 0), "mx_quant_cols_dy": lambda: k.mx_quant_cols(dy, 0),
+        "k17xw_wgrad": lambda: k.mx_wgrad(mg8c, megc, mx8c, mexc, dwx, 0),
     }
     for fn in cases.values():   # warm-up: code objects, library algorithm choice, dgrad's per-shape choice
         for _ in range(3):
@@ -121,7 +129,17 @@ def measure(name, M, K, N, reps, rounds):
            "k17x_fwd_tflops": round(flop / med["k17x_fwd"] / 1e6, 1),
            "mx_over_fp8": {n: round(med["mx_" + n] / med["fp8_" + n], 3) for n in ("fwd", "dgrad")},
            "mx_over_bf16": {n: round(med["mx_" + n] / med["bf16_" + n], 3) for n in ("fwd", "dgrad")},
-           "saved_activation_bytes": {"fp8": 2 * M * K, "fp8_wgrad": M * K + 8}}   # bf16 x / e4m3 x8 + its scale pair
+           "k17xw_wgrad_tflops": round(flop / med["k17xw_wgrad"] / 1e6, 1),
+           "wgrad_ratio_k17xw_over_bf16": round(med["k17xw_wgrad"] / med["bf16_wgrad"], 3),
+           "wgrad_ratio_k17xw_over_k17w": round(med["k17xw_wgrad"] / med["k17w_wgrad"], 3),
+           "k17w_spread": round(max(us["k17w_wgrad"]) / min(us["k17w_wgrad"]), 3),
+           "mx_quant_cols_over_mx_quant": {n: round(med["mx_quant_cols_" + n] / med["mx_quant_" + n], 3) for n in ("x", "dy")},
+           # what differs between fp8="mx_wgrad" and fp8="mx" in one forward + backward: both quantisers and the wgrad
+           "mx_wgrad_over_mx": round((med["mx_quant_cols_x"] + med["mx_quant_cols_dy"] + med["k17xw_wgrad"])
+                                     / (med["mx_quant_x"] + med["mx_quant_dy"] + med["bf16_wgrad"]), 3),
+           # bf16 x / e4m3 x8 + its scale pair / bf16 x / token-blocked e4m3 image + a scale byte per 32 tokens and column
+           "saved_activation_bytes": {"fp8": 2 * M * K, "fp8_wgrad": M * K + 8, "mx": 2 * M * K,
+                                      "mx_wgrad": M * K + (M + 31) // 32 * K}}
     print(json.dumps(rec), flush=True)
     return rec
 

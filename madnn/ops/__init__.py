@@ -2326,8 +2326,9 @@ def gelu_mlp(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: 
 
 # --------------------------------------------------------------------------- K17 (fp8 Linear)
 # ops.linear(fp8=None) takes the fp8 path (opt-in): False, True, "wgrad" (the weight gradient on K17W too) or
-# "mx" (block-scaled operands on K17X)
-FP8_LINEAR = {"0": False, "wgrad": "wgrad", "mx": "mx"}.get(os.environ.get("MADNN_FP8_LINEAR", "0"), True)
+# "mx" (block-scaled operands on K17X) or "mx_wgrad" (that with the weight gradient on K17XW)
+FP8_LINEAR = {"0": False, "wgrad": "wgrad", "mx": "mx", "mx_wgrad": "mx_wgrad"}.get(
+    os.environ.get("MADNN_FP8_LINEAR", "0"), True)
 _FP8_FMT = {"e4m3": 0, "e5m2": 1}
 
 
@@ -2461,20 +2462,29 @@ def _fp8_linear_ok(x, weight, bias, residual, supported=fp8_linear_supported) ->
 
 
 # --------------------------------------------------------------------------- K17X (MX fp8 Linear)
-def mx_quantize(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False):
+def mx_quantize(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False, columns: bool = False):
     """``(q, e, qt, et)``: the 2-D bf16 ``x`` [R, C] in the OCP MX format -- blocks of 32 along C, each with its
     own E8M0 scale byte ``e`` [R, C / 32] (uint8, value ``2^(e - 127)``) taken from the block's amax, elements
     cast to ``torch.float8_e4m3fn`` / ``float8_e5m2`` (``reference.mx_quantize``).  With ``transpose`` the same
     launch also quantises ``x.t()``: ``qt`` [C, R] in blocks along R with ``et`` [C, R / 32] (its own scales, not
     a transpose of ``q``); ``None`` otherwise.  One launch, one read of ``x``, no global amax.  ``C % 32 == 0``,
     and ``R % 32 == 0`` with ``transpose``.  ``e`` / ``et`` are views of row-padded buffers that
-    :func:`mx_gemm` reads in place.  Plain torch on CPU tensors."""
+    :func:`mx_gemm` reads in place.  With ``columns`` (not together with ``transpose``) the third and fourth
+    results are instead ``(qc, ec)``, what :func:`mx_wgrad` reads: ``qc`` [R, C] row-major, quantised in blocks of
+    32 ROWS per column with ``ec`` uint8 [ceil(R / 32), C] (``reference.mx_quantize_columns``), same launch, any
+    ``R``.  Plain torch on CPU tensors."""
     if fmt not in _FP8_FMT:
         raise ValueError(f"mx_quantize: fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
     if x.dim() != 2:
         raise ValueError("mx_quantize: x must be 2-D")
+    if columns and transpose:
+        raise ValueError("mx_quantize: columns and transpose cannot be combined")
     if not _is_dev(x):
+        if columns:
+            return (*reference.mx_quantize(x, fmt), *reference.mx_quantize_columns(x, fmt))
         return (*reference.mx_quantize(x, fmt), *(reference.mx_quantize(x.t(), fmt) if transpose else (None, None)))
+    if columns:
+        return _need_native("mx_quantize").mx_quant_cols(_fp8_rows(x), _FP8_FMT[fmt])
     q, e, qt, et = _need_native("mx_quantize").mx_quant(_fp8_rows(x), _FP8_FMT[fmt], transpose)
     return q, e, (qt if transpose else None), (et if transpose else None)
 
@@ -2509,6 +2519,41 @@ def mx_gemm(a8: torch.Tensor, ea: torch.Tensor, b8: torch.Tensor, eb: torch.Tens
     return _need_native("mx_gemm").mx_gemm(a8, _mx_scales(ea, k), b8, _mx_scales(eb, k), bias, residual)
 
 
+def _mx_col_scales(e: torch.Tensor) -> torch.Tensor:
+    """Column-blocked scale bytes ``e`` [ceil(M / 32), columns] as K17XW fetches them, one aligned 32-bit word per
+    4 columns: ``e`` itself if its rows are contiguous and 4-B aligned (what :func:`mx_quantize` returns), else a
+    contiguous copy."""
+    if e.stride(1) == 1 and e.stride(0) % 4 == 0 and e.stride(0) >= e.shape[1] and e.data_ptr() % 4 == 0:
+        return e
+    return e.contiguous()
+
+
+def mx_wgrad(dy8: torch.Tensor, eg: torch.Tensor, x8: torch.Tensor, ex: torch.Tensor,
+             out: Optional[torch.Tensor] = None, splits: int = 0) -> torch.Tensor:
+    """K17XW: bf16 ``dq(dy8, eg).T @ dq(x8, ex)`` [N, K] for fp8 ``dy8`` [M, N] and ``x8`` [M, K] (each e4m3fn or
+    e5m2, row-major: the token index strided in both) with uint8 E8M0 scales per 32 tokens and column, ``eg``
+    [ceil(M / 32), N] and ``ex`` [ceil(M / 32), K] (``dq(q, e)[m, c] = q[m, c] * 2^(e[m // 32, c] - 127)``, what
+    ``mx_quantize(columns=True)`` makes), the scaling done by the MFMA; fp32 accumulation, one rounding.  Any
+    ``M``; column counts that are no multiple of 16 are padded as in :func:`fp8_wgrad`.  Scales are read in place
+    when their rows are 4-B aligned, copied otherwise.  ``out`` and ``splits`` as in :func:`fp8_wgrad`.  Plain
+    torch on CPU tensors."""
+    blocks = (dy8.shape[0] + 31) // 32
+    if eg.dtype != torch.uint8 or ex.dtype != torch.uint8 or eg.shape != (blocks, dy8.shape[1]) \
+            or ex.shape != (blocks, x8.shape[1]):
+        raise ValueError("mx_wgrad: scales must be uint8 [ceil(M / 32), columns]")
+    if not _is_dev(dy8):
+        dw = (reference.mx_dequantize_columns(dy8, eg).t() @ reference.mx_dequantize_columns(x8, ex)).to(torch.bfloat16)
+        return dw if out is None else out.copy_(dw)
+    k = _need_native("mx_wgrad")
+    n, kk = dy8.shape[1], x8.shape[1]
+    if n % 16 or kk % 16:
+        pad = lambda t: F.pad(t.view(torch.uint8), (0, -t.shape[1] % 16)).view(t.dtype)  # noqa: E731
+        epad = lambda e: F.pad(e, (0, -e.shape[1] % 16), value=127)  # noqa: E731
+        dw = k.mx_wgrad(pad(dy8), epad(eg), pad(x8), epad(ex), None, splits)[:n, :kk]
+        return dw.contiguous() if out is None else out.copy_(dw)
+    return k.mx_wgrad(dy8, _mx_col_scales(eg), x8, _mx_col_scales(ex), out, splits)
+
+
 def mx_linear_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
     """Whether ``linear(x, weight, fp8="mx")`` runs K17X: as :func:`fp8_linear_supported`, with in- and
     out-features multiples of 32 (whole MX blocks in both reduction directions)."""
@@ -2522,40 +2567,60 @@ class _LinearMxFn(torch.autograd.Function):
     same launch, W^T in blocks along out-features; one K17X GEMM with bias and residual in its epilogue.
     Saved: bf16 x, the out-blocked weight image and its scales.  Backward: dy quantised in blocks along
     out-features, dx = K17X(dy8, w8t); weight, bias and residual gradients exactly as :class:`_LinearFp8Fn`
-    without ``wgrad`` (bf16 :func:`_weight_grad` on the saved x)."""
+    without ``wgrad`` (bf16 :func:`_weight_grad` on the saved x).
+
+    ``wgrad`` (``ops.linear(fp8="mx_wgrad")``): the weight gradient runs on K17XW.  Its reduction is the token, so
+    x and dy are quantised a second time in blocks of 32 tokens per column -- by the launches that make their row
+    images (``mx_quant_cols``).  Saved is that e4m3 image of x with its scales (1 + 1/32 B per element) instead of
+    the bf16 x, and dW goes into the reducer's bucket slot as in :class:`_LinearFp8Fn`."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual):
+    def forward(ctx, x, weight, bias, residual, wgrad=False):
         k = _need_native("mx linear")
         n = weight.shape[0]
-        x8, ex, _, _ = k.mx_quant(_fp8_rows(x), 0, False)
+        if wgrad:
+            x8, ex, x8c, exc = k.mx_quant_cols(_fp8_rows(x), 0)
+        else:
+            x8, ex, _, _ = k.mx_quant(_fp8_rows(x), 0, False)
         w8, ew, w8t, ewt = k.mx_quant(_fp8_rows(weight), 0, True)
         res2 = residual.reshape(-1, n).contiguous() if residual is not None else None
         y = k.mx_gemm(x8, ex, w8, ew, bias, res2)
         ctx.bias_dtype = bias.dtype if bias is not None else None
         ctx.param = weight
         ctx.has_res = residual is not None
-        ctx.x_shape = x.shape
-        ctx.save_for_backward(x, w8t, ewt)
+        ctx.wgrad, ctx.x_shape = wgrad, x.shape
+        ctx.save_for_backward(*((x8c, exc, w8t, ewt) if wgrad else (x, w8t, ewt)))
         return y.view(*x.shape[:-1], n)
 
     @staticmethod
     def backward(ctx, g):
-        x, w8t, ewt = ctx.saved_tensors
+        *xs, w8t, ewt = ctx.saved_tensors
         db = dx = dw = None
         if ctx.bias_dtype is not None and ctx.needs_input_grad[2]:
             db = _out_bias_grad(g, ctx.bias_dtype)
         g2 = g.reshape(-1, g.shape[-1])
         if not g2.is_contiguous():
             g2 = g2.contiguous()
-        if ctx.needs_input_grad[0]:
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        if need_dx or (ctx.wgrad and need_dw):
             k = _need_native("mx linear")
-            g8, eg, _, _ = k.mx_quant(g2, 0, False)
+            if ctx.wgrad and need_dw:
+                g8, eg, g8c, egc = k.mx_quant_cols(g2, 0)
+            else:
+                g8, eg, _, _ = k.mx_quant(g2, 0, False)
+        if need_dx:
             dx = k.mx_gemm(g8, eg, w8t, ewt, None, None).view(ctx.x_shape)
-        if ctx.needs_input_grad[1]:
-            dw = _weight_grad(g2, x.reshape(-1, ctx.x_shape[-1]), ctx.param)
+        if need_dw and ctx.wgrad:
+            x8c, exc = xs
+            sink = grad_sink(ctx.param)
+            if sink is not None and not (sink.dtype == torch.bfloat16 and sink.is_contiguous()
+                                         and sink.data_ptr() % 16 == 0):
+                sink = None
+            dw = k.mx_wgrad(g8c, egc, x8c, exc, sink, 0)
+        elif need_dw:
+            dw = _weight_grad(g2, xs[0].reshape(-1, ctx.x_shape[-1]), ctx.param)
         ctx.param = None
-        return dx, dw, db, (g if ctx.has_res else None)
+        return dx, dw, db, (g if ctx.has_res else None), None
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, gelu: bool = False,
@@ -2573,20 +2638,23 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     as well: the backward keeps the e4m3 image of ``x`` instead of ``x`` (``reference.linear_fp8(wgrad=True)``).
     ``fp8="mx"`` (``MADNN_FP8_LINEAR=mx``) is the MX recipe instead of the per-tensor one: x, W and dy as e4m3
     with one E8M0 scale per 32 elements along the reduction, forward and data gradient on the block-scaled GEMM
-    K17X (:class:`_LinearMxFn`) where :func:`mx_linear_supported` holds, ``reference.linear_mx`` on CPU tensors."""
+    K17X (:class:`_LinearMxFn`) where :func:`mx_linear_supported` holds, ``reference.linear_mx`` on CPU tensors.
+    ``fp8="mx_wgrad"`` (``MADNN_FP8_LINEAR=mx_wgrad``) is the MX path with the weight gradient on the block-scaled
+    GEMM K17XW as well: x and dy are also quantised in blocks of 32 tokens per column, and the backward keeps that
+    e4m3 image of ``x`` instead of ``x`` (``reference.linear_mx(wgrad=True)``)."""
     if residual is not None and residual.shape[:-1] != x.shape[:-1]:
         raise ValueError("linear: residual must have the output's shape")
     mode = FP8_LINEAR if fp8 is None else fp8
-    if mode not in (None, False, True, "wgrad", "mx"):
-        raise ValueError(f"linear: fp8 must be None, a bool, 'wgrad' or 'mx', not {fp8!r}")
+    if mode not in (None, False, True, "wgrad", "mx", "mx_wgrad"):
+        raise ValueError(f"linear: fp8 must be None, a bool, 'wgrad', 'mx' or 'mx_wgrad', not {fp8!r}")
     if mode and not gelu:
         if fp8 and not _is_dev(x):
-            if mode == "mx":
-                return reference.linear_mx(x, weight, bias, residual)
+            if mode in ("mx", "mx_wgrad"):
+                return reference.linear_mx(x, weight, bias, residual, mode == "mx_wgrad")
             return reference.linear_fp8(x, weight, bias, residual, wgrad=mode == "wgrad")
-        if mode == "mx":
+        if mode in ("mx", "mx_wgrad"):
             if _fp8_linear_ok(x, weight, bias, residual, mx_linear_supported):
-                return _LinearMxFn.apply(x, weight, bias, residual)
+                return _LinearMxFn.apply(x, weight, bias, residual, mode == "mx_wgrad")
         elif _fp8_linear_ok(x, weight, bias, residual):
             return _LinearFp8Fn.apply(x, weight, bias, residual, mode == "wgrad")
     if not torch.is_grad_enabled() or (not force_fn and (not _is_dev(x) or weight.shape[0] % 8)):
@@ -2610,7 +2678,7 @@ __all__ = [
     "linear", "linear_tee", "gelu_mlp", "bias_grad", "gelu_tanh", "grad_sink", "wgrad_into", "tuned_wgrad", "dgrad",
     "dgrad_dgelu", "load_tuning_table", "export_choices", "sync_choices", "tuning_timings", "tuning_measurements",
     "fp8_quantize", "fp8_gemm", "fp8_wgrad", "fp8_linear_supported", "FP8_LINEAR",
-    "mx_quantize", "mx_gemm", "mx_linear_supported",
+    "mx_quantize", "mx_gemm", "mx_wgrad", "mx_linear_supported",
 ]
 
 if os.environ.get("MADNN_EAGER_LOAD", "0") == "1":

@@ -397,5 +397,17 @@ hipError_t madnn_mx_quant(const void* x, int64_t ldx, int64_t R, int64_t C, int 
 hipError_t madnn_mx_gemm(const void* a, int fmt_a, const void* ea, int64_t ldea, const void* b, int fmt_b,
                          const void* eb, int64_t ldeb, const void* bias, int bias_f32, const void* res, void* out,
                          int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, hipStream_t stream);
+// MX quantiser with the column-blocked image (one launch): q / e as madnn_mx_quant, and qc: fp8 [R][C] quantised in
+// blocks of 32 ROWS per column with ec: E8M0 bytes [ceil(R / 32)][ldec] (byte c of row B: rows 32 B .. + 31 of
+// column c; ldec % 4 == 0, ldec >= C, 4-B aligned).  Any R > 0 (rows past R count as zeros), C % 32 == 0.
+hipError_t madnn_mx_quant_cols(const void* x, int64_t ldx, int64_t R, int64_t C, int fmt, void* q, void* e,
+                               int64_t lde, void* qc, void* ec, int64_t ldec, hipStream_t stream);
+// K17XW: dw[N][K] (bf16, contiguous) = sum_m dy8[m][n] 2^(eg[m / 32][n] - 127) x8[m][k] 2^(ex[m / 32][k] - 127);
+// dy8 / x8 / ws / splits as madnn_fp8_wgrad (madnn_fp8_wgrad_splits gives the split count), eg / ex the
+// column-blocked scale bytes madnn_mx_quant_cols writes (row strides ldeg >= N / ldex >= K, multiples of 4, 4-B
+// aligned).  Any M > 0, N % 16 == 0, K % 16 == 0.
+hipError_t madnn_mx_wgrad(const void* dy8, int fmt_g, const void* eg, int64_t ldeg, const void* x8, int fmt_x,
+                          const void* ex, int64_t ldex, void* dw, float* ws, int splits, int64_t M, int64_t N,
+                          int64_t K, int64_t ldg, int64_t ldx, hipStream_t stream);
 
 }  // extern "C"

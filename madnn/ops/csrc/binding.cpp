@@ -1847,6 +1847,66 @@ at::Tensor mx_gemm(const at::Tensor& a, const at::Tensor& ea, const at::Tensor& 
   return y;
 }
 
+// x: bf16 [R, C] -> (q [R, C], e [R, C / 32] as mx_quant, qc [R, C], ec [ceil(R / 32), C]): the row image and, from
+// the same launch, the image blocked along R (32 rows of a column share a byte of ec) that mx_wgrad reads in place
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> mx_quant_cols(const at::Tensor& x, int64_t fmt) {
+  fp8_rows_check(x, "x", 8);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "mx_quant_cols: x must be bf16");
+  TORCH_CHECK(fmt == 0 || fmt == 1, "mx_quant_cols: fmt 0 (e4m3fn) or 1 (e5m2)");
+  const int64_t R = x.size(0), C = x.size(1);
+  TORCH_CHECK(R > 0 && C > 0 && C % 32 == 0, "mx_quant_cols: C % 32 == 0, got R=", R, " C=", C);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const auto qopt = x.options().dtype(fmt == 1 ? at::kFloat8_e5m2 : at::kFloat8_e4m3fn);
+  const auto eopt = x.options().dtype(at::kByte);
+  const int64_t lde = mx_scale_ld(C);
+  at::Tensor q = at::empty({R, C}, qopt), e = at::empty({R, lde}, eopt);
+  at::Tensor qc = at::empty({R, C}, qopt), ec = at::empty({(R + 31) / 32, C}, eopt);
+  check(madnn_mx_quant_cols(x.data_ptr(), x.stride(0), R, C, (int)fmt, q.data_ptr(), e.data_ptr(), lde, qc.data_ptr(),
+                            ec.data_ptr(), C, cur_stream(x)),
+        "mx_quant_cols");
+  return {q, e.narrow(1, 0, C / 32), qc, ec};
+}
+
+// column-blocked scale bytes [ceil(M / 32), cols] that K17XW can read in place: see madnn_mx_wgrad
+void mx_col_scale_check(const at::Tensor& e, const char* name, int64_t M, int64_t cols) {
+  check_dev(e, name);
+  TORCH_CHECK(e.scalar_type() == at::kByte && e.dim() == 2 && e.size(0) == (M + 31) / 32 && e.size(1) == cols,
+              "mx_wgrad: ", name, " must be uint8 [ceil(M / 32), columns]");
+  TORCH_CHECK(e.stride(1) == 1 && e.stride(0) % 4 == 0 && e.stride(0) >= cols &&
+                  reinterpret_cast<uintptr_t>(e.data_ptr()) % 4 == 0,
+              "mx_wgrad: ", name, " needs 4-B aligned rows (ops.mx_wgrad makes them)");
+}
+
+// K17XW: dw [N, K] bf16 = dq(dy8 [M, N], eg)^T . dq(x8 [M, K], ex), into `out` when given; splits 0: the kernel's choice
+at::Tensor mx_wgrad(const at::Tensor& dy8, const at::Tensor& eg, const at::Tensor& x8, const at::Tensor& ex,
+                    const c10::optional<at::Tensor>& out, int64_t splits) {
+  fp8_rows_check(dy8, "dy8", 16);
+  fp8_rows_check(x8, "x8", 16);
+  const int fg = fp8_fmt(dy8, "dy8"), fx = fp8_fmt(x8, "x8");
+  const int64_t M = dy8.size(0), N = dy8.size(1), K = x8.size(1);
+  TORCH_CHECK(x8.size(0) == M && M > 0 && N > 0 && K > 0 && N % 16 == 0 && K % 16 == 0 && splits >= 0 && splits <= 4096,
+              "mx_wgrad: dy8 [M, N], x8 [M, K] with N % 16 == 0 and K % 16 == 0, got M=", M, " N=", N, " K=", K,
+              " splits=", splits);
+  mx_col_scale_check(eg, "eg", M, N);
+  mx_col_scale_check(ex, "ex", M, K);
+  at::hip::HIPGuardMasqueradingAsCUDA guard(dy8.device());
+  at::Tensor dw;
+  if (out.has_value() && out->defined()) {
+    gemm_check(*out, "out");
+    TORCH_CHECK(out->scalar_type() == at::kBFloat16 && out->numel() == N * K, "mx_wgrad: out must be bf16 and hold N x K");
+    dw = *out;
+  } else {
+    dw = at::empty({N, K}, dy8.options().dtype(at::kBFloat16));
+  }
+  const int sp = splits > 0 ? (int)splits : madnn_fp8_wgrad_splits(M, N, K);
+  at::Tensor ws = sp > 1 ? at::empty({sp, N, K}, dy8.options().dtype(at::kFloat)) : at::Tensor();
+  check(madnn_mx_wgrad(dy8.data_ptr(), fg, eg.data_ptr(), eg.stride(0), x8.data_ptr(), fx, ex.data_ptr(), ex.stride(0),
+                       dw.data_ptr(), sp > 1 ? ws.data_ptr<float>() : nullptr, sp, M, N, K, dy8.stride(0), x8.stride(0),
+                       cur_stream(dy8)),
+        "mx_wgrad");
+  return dw;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(madnn, m) {
@@ -1856,6 +1916,8 @@ TORCH_LIBRARY(madnn, m) {
   m.def("fp8_wgrad_splits(int M, int N, int K) -> int", &fp8_wgrad_splits);
   m.def("mx_quant(Tensor x, int fmt, bool transpose) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("mx_gemm(Tensor a, Tensor ea, Tensor b, Tensor eb, Tensor? bias, Tensor? res) -> Tensor");
+  m.def("mx_quant_cols(Tensor x, int fmt) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("mx_wgrad(Tensor dy8, Tensor eg, Tensor x8, Tensor ex, Tensor? out, int splits) -> Tensor");
   m.def("hwq_batch(Tensor kinds, Tensor msgs, Tensor(a!) a, Tensor(b!) b, int epoch, int timeout_us, Tensor(c!) ok, "
         "Tensor ok_index) -> ()");
   m.def("hwq_spin(Tensor like, int spin_us) -> ()");
@@ -2035,6 +2097,8 @@ TORCH_LIBRARY_IMPL(madnn, CUDA, m) {
   m.impl("fp8_wgrad", fp8_wgrad);
   m.impl("mx_quant", mx_quant);
   m.impl("mx_gemm", mx_gemm);
+  m.impl("mx_quant_cols", mx_quant_cols);
+  m.impl("mx_wgrad", mx_wgrad);
   m.impl("conv3x3_fwd", conv3x3_fwd);
   m.impl("conv3x3_fwd_s2", conv3x3_fwd_s2);
   m.impl("conv3x3_wgrad", conv3x3_wgrad);

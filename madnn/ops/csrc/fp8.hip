@@ -1,7 +1,8 @@
 // K17 -- fp8 GEMM on v_mfma_f32_32x32x64_f8f6f4 for gfx950, and the per-tensor quantiser that feeds it:
 // the forward and the data gradient of an opt-in FP8 Linear (ops.linear(fp8=True), madnn.nn.Fp8Linear).
 // K17W, the weight gradient of that Linear on the same MFMA (ops.linear(fp8="wgrad")), has its own header below,
-// and so have K17X, the MX block-scaled GEMM (ops.linear(fp8="mx")), and its one-pass quantiser.
+// and so have K17X, the MX block-scaled GEMM (ops.linear(fp8="mx")), its one-pass quantiser, and K17XW, the MX
+// weight gradient (ops.linear(fp8="mx_wgrad")) with the quantiser's column-blocked mode.
 //
 // Formats: OCP e4m3fn (activations, weights) and e5m2 (output gradients), bit for bit torch's
 // float8_e4m3fn / float8_e5m2.  Scaling is per tensor and current: scale = 2^floor(log2(FMAX / amax)) of the
@@ -952,6 +953,337 @@ hipError_t launch_mx_quant(const uint16_t* x, int64_t ldx, int64_t R, int C, uin
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ MX column-blocked quantiser, K17XW
+// The weight gradient dW[n][k] = sum_m dy[m][n] x[m][k] reduces over the token m, so MX wants x and dy blocked
+// along m: 32 tokens of ONE column share a scale byte.  mx_quant_cols_kernel writes, from the one read of its
+// 64 x 64 tile, the row image (q, e: mx_quant_kernel's code, bit for bit) and the column-blocked image
+//   qc [R][C] fp8, row-major as q;   ec [ceil(R / 32)][ldec] uint8, byte [B][c]: rows 32 B .. 32 B + 31 of column c.
+// qc is a second quantisation with its own scales (same formula: mx_scale_byte of the block's bit-pattern amax,
+// factor 2^(127 - e), explicit clamp, cast), not a copy of q.  R is any positive number: rows at or past R enter
+// a block's amax as zeros and are not stored, the last block may be partial.  ldec % 4 == 0, ldec >= C, base 4-B
+// aligned.
+// Column amax -- chosen: shuffles plus a small LDS exchange (not the TR path's tile read by columns, which hands
+// a lane a column, so the stores would run down columns; here a lane keeps its 16-B row run and the qc store is
+// the q store).  A lane's 16 values are 8 words of two bit patterns; the maximum over the 16 rows of a wave is
+// taken on the packed words (v_pk_max_u16, sign bits cleared) with xor-shuffles over the row lanes (offsets 4, 8,
+// 16, 32), 8 words x 4 steps.  A 32-row block is two waves (rows 16 w .. + 15 are wave w): lanes 0..3 of each wave
+// write its 64 column maxima (128 B) to LDS as two 16-B stores, and after one barrier every lane reads the partner
+// wave's 32 B for its columns.  Banks: the four writing lanes cover 32 consecutive words; a wave's read is 4
+// distinct 32-B runs of one 128-B row (the 16 lanes of a run read the same words: a broadcast), so neither
+// conflicts.  Each of the 16 columns then has its own factor; 16 B of qc leave per lane, and the lanes of rows 0
+// and 32 of the tile store their 16 scale bytes as four aligned words.
+//
+// K17XW: dW[N][K] (bf16) = sum_m (dy8[m][n] 2^(eg[m / 32][n] - 127)) (x8[m][k] 2^(ex[m / 32][k] - 127)) on
+// v_mfma_scale_f32_32x32x64_f8f6f4, both operands row-major and token-strided with column-blocked scales (above).
+// K17W's, unchanged: the 256 x 256 tile and 8 waves as 2 x 4, the 128-token step as two [128][256 B] images per
+// stage and 2 stages, the 1-KiB DMA pieces with the s ^ 2 (token & 7) slot swizzle, ds_read_b64_tr_b8 fragments
+// with x as the first operand (cbsz: x's format, blgp: dy's), the split over whole 128-token steps
+// (madnn_fp8_wgrad_splits), the fp32 slabs added in split order, the two-half LDS epilogue.  No scale factor in
+// the epilogue or the reduce.
+// Block meets scale: the hardware takes the scale of k block j (k 32 j .. + 31 of the 64-deep MFMA) from the lane
+// of that row in half j, and a lane of half h holds hardware k 16 h .. + 15 in register bytes 0..15 and
+// 32 + 16 h .. + 15 in bytes 16..31 (K17X's header).  K17W gives half h tokens 32 h .. + 31, where a token only has
+// to meet itself; here the four transposed reads of a fragment fetch tokens 16 h + 8 q .. + 7 (q = 0, 1: the MFMA
+// step's first 32-token block) and 32 + 16 h + 8 (q - 2) .. + 7 (q = 2, 3: its second) -- tr_lane_off_mx /
+// frag_tr_mx.  Inside a block every token of a column has the same scale, so the byte order inside one read does
+// not matter as long as both operands share it (same code).  Bank argument: the eight token rows of one read are
+// still r0 .. r0 + 7 with r0 % 8 == 0 (16 h, 8, 32 and 40 are multiples of 8), so the XOR term is still
+// 2 ((lane & 15) >> 1) and K17W's argument holds unchanged; s, q and the stage stay immediate offsets.
+// Scales ride the data ring (K17X): a 128-token step needs 4 block rows x 256 columns per operand = 1 KiB, ONE
+// glds4 piece per wave and stage, issued after its 8 data pieces -- waves 0..3 dy's scales, 4..7 x's; wave w & 3
+// takes block w & 3 of the step, lane l the word of columns 4 (l ^ 8 (w & 1)) .. + 3 of the tile.  LDS: 2 x 64 KiB
+// + 2 x 2 KiB = kXLds.  Counted wait vmcnt(9); the RAW / WAR argument is K17X's (the bytes live and die with
+// their stage).  MFMA s of a step: lane (column c, half h) supplies byte [2 s + h][c] of its operand's scale
+// image with op_sel 0 -- one ds_read_u8 per accumulator row / column block, six per MFMA step and wave (4 dy,
+// 2 x).  Conflicts: the 32 lanes of a half read 32 consecutive bytes = 8 words, four lanes a word (broadcast);
+// the other half reads the next block row, 256 B = 64 banks further, i.e. the SAME banks -- hence the XOR 8 on the
+// word index of odd block rows (applied to the DMA source column and as c ^ 32 h to the read), which puts it on
+// the other 8 words of the aligned 16-word group: 16 different banks per read.
+// Ragged: M any positive number, N and K multiples of 16.  Data lanes outside read g_zero16 as in K17W.  A scale
+// lane whose token block is at or past ceil(M / 32), or whose column word is at or past N / K, reads g_one_word;
+// no address past the tensors is formed.  The quantiser never writes 255, so zero data never meets a NaN scale.
+// tests/test_mx_wgrad_gpu.py::test_scale_routing_exact (independent scales per token block and column) is the proof.
+__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
+  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+
+template <int FMT>
+__global__ __launch_bounds__(kQThreads) void mx_quant_cols_kernel(const uint16_t* __restrict__ x, int64_t ldx, int64_t R,
+                                                                  int C, uint8_t* __restrict__ q, uint8_t* __restrict__ e,
+                                                                  int64_t lde, uint8_t* __restrict__ qc,
+                                                                  uint8_t* __restrict__ ec, int64_t ldec) {
+  __shared__ __attribute__((aligned(16))) unsigned cmax[kQThreads / kWave][kQTile / 2];
+  const int ctiles = (C + kQTile - 1) / kQTile;
+  const int64_t rt = blockIdx.x / ctiles;
+  const int ct = (int)(blockIdx.x - rt * ctiles);
+  const int tid = threadIdx.x, lr = tid >> 2, lq = tid & 3, wv = tid >> 6;
+  const int64_t r = rt * kQTile + lr;
+  const int c = ct * kQTile + 16 * lq;
+  const bool in = r < R && c < C;
+  u32x4 a = u32x4{0u, 0u, 0u, 0u}, b = a;
+  if (in) {
+    a = *reinterpret_cast<const u32x4*>(x + r * ldx + c);
+    b = *reinterpret_cast<const u32x4*>(x + r * ldx + c + 8);
+  }
+  // ---- row image: mx_quant_kernel's
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m = amax_word(amax_word(m, a[i]), b[i]);
+  const unsigned mo = (unsigned)__shfl_xor((int)m, 1, kWave);
+  const unsigned eb = mx_scale_byte<FMT>(m > mo ? m : mo);
+  const unsigned eb2 = (unsigned)__shfl_xor((int)eb, 2, kWave);
+  if (in) {
+    const float f = __uint_as_float((254u - eb) << 23);
+    *reinterpret_cast<u32x4*>(q + r * C + c) = u32x4{mx_cvt4<FMT>(a[0], a[1], f), mx_cvt4<FMT>(a[2], a[3], f),
+                                                     mx_cvt4<FMT>(b[0], b[1], f), mx_cvt4<FMT>(b[2], b[3], f)};
+    if (lq == 0) *reinterpret_cast<uint16_t*>(e + r * lde + 2 * ct) = (uint16_t)(eb | (eb2 << 8));
+  }
+  // ---- column image (header): amax of the wave's 16 rows per column, then the partner wave's
+  unsigned w[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    w[i] = a[i] & 0x7fff7fffu;
+    w[4 + i] = b[i] & 0x7fff7fffu;
+  }
+#pragma unroll
+  for (int off = 4; off < kWave; off <<= 1)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = pk_max_u16(w[i], (unsigned)__shfl_xor((int)w[i], off, kWave));
+  if ((tid & 60) == 0) {
+    *reinterpret_cast<u32x4*>(&cmax[wv][8 * lq]) = u32x4{w[0], w[1], w[2], w[3]};
+    *reinterpret_cast<u32x4*>(&cmax[wv][8 * lq + 4]) = u32x4{w[4], w[5], w[6], w[7]};
+  }
+  __syncthreads();
+  const u32x4 o0 = *reinterpret_cast<const u32x4*>(&cmax[wv ^ 1][8 * lq]);
+  const u32x4 o1 = *reinterpret_cast<const u32x4*>(&cmax[wv ^ 1][8 * lq + 4]);
+  u32x4 oq, oe;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {  // output word j: columns 4 j .. 4 j + 3 = source words 2 j, 2 j + 1
+    const unsigned m0 = pk_max_u16(w[2 * j], j < 2 ? o0[2 * j] : o1[2 * j - 4]);
+    const unsigned m1 = pk_max_u16(w[2 * j + 1], j < 2 ? o0[2 * j + 1] : o1[2 * j - 3]);
+    const unsigned e0 = mx_scale_byte<FMT>(m0 & 0xffffu), e1 = mx_scale_byte<FMT>(m0 >> 16);
+    const unsigned e2 = mx_scale_byte<FMT>(m1 & 0xffffu), e3 = mx_scale_byte<FMT>(m1 >> 16);
+    const unsigned s0 = j < 2 ? a[2 * j] : b[2 * j - 4], s1 = j < 2 ? a[2 * j + 1] : b[2 * j - 3];
+    oq[j] = cvt4<FMT>(mx_fit<FMT>(bf16_lo(s0), __uint_as_float((254u - e0) << 23)),
+                      mx_fit<FMT>(bf16_hi(s0), __uint_as_float((254u - e1) << 23)),
+                      mx_fit<FMT>(bf16_lo(s1), __uint_as_float((254u - e2) << 23)),
+                      mx_fit<FMT>(bf16_hi(s1), __uint_as_float((254u - e3) << 23)));
+    oe[j] = e0 | (e1 << 8) | (e2 << 16) | (e3 << 24);
+  }
+  if (in) {
+    *reinterpret_cast<u32x4*>(qc + r * C + c) = oq;
+    if ((lr & 31) == 0) {  // the block's first row is inside, so the block exists; ldec % 4 == 0: aligned words
+      unsigned* const ep = reinterpret_cast<unsigned*>(ec + (2 * rt + (lr >> 5)) * ldec + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ep[j] = oe[j];
+    }
+  }
+}
+
+template <int FMT>
+hipError_t launch_mx_quant_cols(const uint16_t* x, int64_t ldx, int64_t R, int C, uint8_t* q, uint8_t* e, int64_t lde,
+                                uint8_t* qc, uint8_t* ec, int64_t ldec, unsigned tiles, hipStream_t s) {
+  hipLaunchKernelGGL((mx_quant_cols_kernel<FMT>), dim3(tiles), dim3(kQThreads), 0, s, x, ldx, R, C, q, e, lde, qc, ec, ldec);
+  return hipGetLastError();
+}
+
+constexpr int kXWScale = 2 * 4 * kWRow;    // scale bytes of one stage: dy [4 blocks][256], x [4][256]
+static_assert(kLds + 2 * kXWScale == kXLds, "K17XW uses K17X's LDS budget");
+
+struct XWArgs {
+  const uint8_t* g;      // dy8 [M][N]
+  const uint8_t* x;      // x8 [M][K]
+  const uint8_t* eg;     // [ceil(M / 32)][ldeg]
+  const uint8_t* ex;     // [ceil(M / 32)][ldex]
+  uint16_t* out;         // [N][K] bf16 (splits == 1)
+  float* ws;             // [splits][N][K] fp32 (splits > 1)
+  int64_t ldg, ldx, ldeg, ldex;
+  int64_t M, N, K;
+  int n_tiles, k_tiles, splits;
+  int steps_per;         // 128-token steps per split
+};
+
+// lane part of a fragment's read address for the 32 columns from c0: K17W's with half hh at tokens 16 hh (header)
+__device__ __forceinline__ int tr_lane_off_mx(int c0, int lane) {
+  const int i = lane & 15, r7 = i >> 1;
+  const int slot = ((c0 >> 4) + ((lane >> 4) & 1)) ^ (2 * r7);
+  return (16 * (lane >> 5) + r7) * kWRow + 16 * slot + 8 * (i & 1);
+}
+
+// tokens 16 hh .. + 15 and 32 + 16 hh .. + 15 of MFMA step s for this lane's column: four ds_read_b64_tr_b8
+__device__ __forceinline__ i32x8 frag_tr_mx(const uint8_t* img, int lane_off, int s) {
+  const uint8_t* p = img + lane_off + 64 * s * kWRow;
+  const i32x2 q0 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p));
+  const i32x2 q1 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p + 8 * kWRow));
+  const i32x2 q2 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p + 32 * kWRow));
+  const i32x2 q3 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((lds_i32x2*)(p + 40 * kWRow));
+  return i32x8{q0[0], q0[1], q1[0], q1[1], q2[0], q2[1], q3[0], q3[1]};
+}
+
+// FG / FX: format flags of dy8 and x8
+template <int FG, int FX>
+__global__ __launch_bounds__(kThreads) void mx_wgrad_kernel(const XWArgs p) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[kXLds];
+  const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, l32 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 2, wc = wave & 3;
+
+  const int wid = xcd_group_id(blockIdx.x, gridDim.x);
+  const int tiles = p.n_tiles * p.k_tiles;
+  const int split = wid / tiles, tile = wid - split * tiles;
+  const int64_t n0 = (int64_t)(tile / p.k_tiles) * kT, k0 = (int64_t)(tile % p.k_tiles) * kT;
+  const int64_t mbeg = (int64_t)split * p.steps_per * kWT;
+  int64_t mend = mbeg + (int64_t)p.steps_per * kWT;
+  mend = mend < p.M ? mend : p.M;
+  const int nk = mend > mbeg ? (int)((mend - mbeg + kWT - 1) / kWT) : 0;
+
+  // data DMA sources: K17W's
+  const bool is_g = wave < 4;
+  const uint8_t* const op = is_g ? p.g : p.x;
+  const int64_t ld = is_g ? p.ldg : p.ldx;
+  const int64_t c0 = is_g ? n0 : k0, clim = is_g ? p.N : p.K;
+  const int64_t col_even = c0 + 16 * ((lane & 15) ^ (2 * (lane >> 4)));
+  const int64_t col_odd = c0 + 16 * ((lane & 15) ^ (2 * (4 + (lane >> 4))));
+  const bool ok_even = col_even < clim, ok_odd = col_odd < clim;
+  const int row0 = 32 * (wave & 3) + (lane >> 4);
+  uint8_t* const dma_dst = smem + (is_g ? 0 : kWImage) + (wave & 3) * (kPieces * 1024);
+  // scale piece: block wave & 3 of the step, lane l the word of tile columns 4 (l ^ 8 (wave & 1)) .. + 3 (header)
+  const uint8_t* const eop = is_g ? p.eg : p.ex;
+  const int64_t lde = is_g ? p.ldeg : p.ldex;
+  const int64_t ecol = c0 + 4 * (lane ^ (8 * (wave & 1)));
+  const bool eok = ecol < clim;  // N, K % 16 == 0: a word is inside or outside as a whole
+  const int64_t blocks = (p.M + 31) >> 5;
+  uint8_t* const edst = smem + kLds + (is_g ? 0 : 4 * kWRow) + (wave & 3) * kWRow;
+
+  auto stage = [&](int t) {
+    const int64_t mb = mbeg + (int64_t)t * kWT + row0;
+#pragma unroll
+    for (int e = 0; e < kPieces; ++e) {
+      const int64_t m = mb + 4 * e;
+      const bool in = m < mend && ((e & 1) ? ok_odd : ok_even);
+      const void* s = in ? (const void*)(op + m * ld + ((e & 1) ? col_odd : col_even)) : (const void*)g_zero16;
+      glds16(s, (lds_void*)(dma_dst + (t & 1) * kWStage + e * 1024));
+    }
+    const int64_t blk = ((mbeg + (int64_t)t * kWT) >> 5) + (wave & 3);
+    const void* s = eok && blk < blocks ? (const void*)(eop + blk * lde + ecol) : (const void*)&g_one_word;
+    glds4(s, (lds_void*)(edst + (t & 1) * kXWScale));
+  };
+
+  int goff[4], xoff[2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) goff[a] = tr_lane_off_mx(wr * 128 + 32 * a, lane);
+#pragma unroll
+  for (int b = 0; b < 2; ++b) xoff[b] = tr_lane_off_mx(wc * 64 + 32 * b, lane);
+  // byte [2 s + hh][column ^ 32 hh] of a scale image: + 512 s; column block a (b) is 32 (a ^ hh) bytes along, so an
+  // even and an odd block's offset per operand, + 64 for blocks 2 and 3
+  const int egoff[2] = {hh * kWRow + wr * 128 + l32 + 32 * hh, hh * kWRow + wr * 128 + l32 + 32 * (1 - hh)};
+  const int exoff[2] = {(4 + hh) * kWRow + wc * 64 + l32 + 32 * hh, (4 + hh) * kWRow + wc * 64 + l32 + 32 * (1 - hh)};
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = zero16();
+
+  if (nk > 0) stage(0);
+  for (int t = 0; t < nk; ++t) {
+    if (t + 1 < nk) {
+      stage(t + 1);
+      wait_vmcnt<kPieces + 1>();  // step t's pieces: all but the 9 just issued
+    } else {
+      wait_vmcnt<0>();
+    }
+    barrier();
+    const uint8_t* sg = smem + (t & 1) * kWStage;
+    const uint8_t* sx = sg + kWImage;
+    const uint8_t* se = smem + kLds + (t & 1) * kXWScale;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      i32x8 xf[2], gf[4];
+      unsigned ex[2], eg[4];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) ex[b] = se[exoff[b] + 2 * kWRow * s];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) eg[a] = se[egoff[a & 1] + 2 * kWRow * s + 64 * (a >> 1)];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) xf[b] = frag_tr_mx(sx, xoff[b], s);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) gf[a] = frag_tr_mx(sg, goff[a], s);
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = mfmax<FG, FX, 0>(xf[b], gf[a], acc[a][b], ex[b], eg[a]);
+    }
+    wait_lgkmcnt0();  // this stage's last fragment and scale reads, before the barrier that opens it for step t + 2
+    barrier();
+  }
+
+  // ---- epilogue: K17W's, without a scale factor
+  const bool slab = p.splits > 1;
+  char* ot = reinterpret_cast<char*>(smem);
+  const int c = tid & 31, rr = tid >> 5;
+  const int64_t kg = k0 + 8 * c;
+  float* const ws = slab ? p.ws + (int64_t)split * p.N * p.K : nullptr;
+#pragma unroll 1
+  for (int half = 0; half < 2; ++half) {
+    if (wr == half) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int nl = 32 * a + l32, ch = wc * 16 + 8 * b + 2 * g + hh;
+            const f32x16& v = acc[a][b];
+            *reinterpret_cast<f32x4*>(ot + nl * 1024 + 16 * (ch ^ (nl & 15))) =
+                f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+          }
+    }
+    __syncthreads();
+    if (kg < p.K) {
+#pragma unroll 2
+      for (int i = 0; i < 8; ++i) {
+        const int nl = rr + 16 * i;
+        const int64_t ng = n0 + 128 * half + nl;
+        if (ng >= p.N) break;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(ot + nl * 1024 + 16 * ((2 * c) ^ (nl & 15)));
+        const f32x4 hi = *reinterpret_cast<const f32x4*>(ot + nl * 1024 + 16 * ((2 * c + 1) ^ (nl & 15)));
+        if (slab) {
+          *reinterpret_cast<f32x4*>(ws + ng * p.K + kg) = lo;
+          *reinterpret_cast<f32x4*>(ws + ng * p.K + kg + 4) = hi;
+        } else {
+          const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          store8<kBF16>(p.out, ng * p.K + kg, v);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// out[e] = bf16(sum_s ws[s][e]), slabs added in split order (wgrad8_reduce_kernel without its scale pair)
+__global__ __launch_bounds__(256) void mx_wgrad_reduce_kernel(const float* __restrict__ ws, uint16_t* __restrict__ out,
+                                                              int splits, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 8;
+  for (int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8; e < n; e += stride) {
+    f32x4 lo = *reinterpret_cast<const f32x4*>(ws + e), hi = *reinterpret_cast<const f32x4*>(ws + e + 4);
+    for (int q = 1; q < splits; ++q) {
+      lo += *reinterpret_cast<const f32x4*>(ws + (int64_t)q * n + e);
+      hi += *reinterpret_cast<const f32x4*>(ws + (int64_t)q * n + e + 4);
+    }
+    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    store8<kBF16>(out, e, v);
+  }
+}
+
+template <int FG, int FX>
+hipError_t launch_mx_wgrad(const XWArgs& p, hipStream_t s) {
+  const int64_t grid = (int64_t)p.n_tiles * p.k_tiles * p.splits;
+  hipLaunchKernelGGL((mx_wgrad_kernel<FG, FX>), dim3((unsigned)grid), dim3(kThreads), 0, s, p);
+  return hipGetLastError();
+}
+
 }  // namespace fp8
 }  // namespace madnn
 
@@ -1130,5 +1462,71 @@ extern "C" hipError_t madnn_fp8_wgrad(const void* dy8, int fmt_g, const void* x8
   const int64_t n = N * K;
   hipLaunchKernelGGL(fp8::wgrad8_reduce_kernel, dim3((unsigned)stream_grid(n / 8, 256, 2048)), dim3(256), 0, stream,
                      p.ws, p.out, p.splits, n, inv_g, inv_x);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t madnn_mx_quant_cols(const void* x, int64_t ldx, int64_t R, int64_t C, int fmt, void* q, void* e,
+                                          int64_t lde, void* qc, void* ec, int64_t ldec, hipStream_t stream) {
+  if (R <= 0 || C <= 0 || C % 32 || ldx % 8 || ldx < C || C > 0x7fffffff || (fmt != 0 && fmt != 1))
+    return hipErrorInvalidValue;
+  if (x == nullptr || q == nullptr || e == nullptr || lde % 4 || lde < 4 * ((C + 127) / 128)) return hipErrorInvalidValue;
+  if (qc == nullptr || ec == nullptr || ldec % 4 || ldec < C) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(qc)) % 16 ||
+      (reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(ec)) % 4)
+    return hipErrorInvalidValue;
+  const int64_t tiles = ((R + fp8::kQTile - 1) / fp8::kQTile) * ((C + fp8::kQTile - 1) / fp8::kQTile);
+  if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+  const uint16_t* xp = static_cast<const uint16_t*>(x);
+  uint8_t* qp = static_cast<uint8_t*>(q);
+  uint8_t* ep = static_cast<uint8_t*>(e);
+  uint8_t* qcp = static_cast<uint8_t*>(qc);
+  uint8_t* ecp = static_cast<uint8_t*>(ec);
+  if (fmt == fp8::kE5M2)
+    return fp8::launch_mx_quant_cols<1>(xp, ldx, R, (int)C, qp, ep, lde, qcp, ecp, ldec, (unsigned)tiles, stream);
+  return fp8::launch_mx_quant_cols<0>(xp, ldx, R, (int)C, qp, ep, lde, qcp, ecp, ldec, (unsigned)tiles, stream);
+}
+
+extern "C" hipError_t madnn_mx_wgrad(const void* dy8, int fmt_g, const void* eg, int64_t ldeg, const void* x8, int fmt_x,
+                                     const void* ex, int64_t ldex, void* dw, float* ws, int splits, int64_t M, int64_t N,
+                                     int64_t K, int64_t ldg, int64_t ldx, hipStream_t stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || N % 16 || K % 16 || ldg % 16 || ldx % 16 || ldg < N || ldx < K)
+    return hipErrorInvalidValue;
+  if ((fmt_g != 0 && fmt_g != 1) || (fmt_x != 0 && fmt_x != 1) || splits < 1) return hipErrorInvalidValue;
+  if (dy8 == nullptr || x8 == nullptr || dw == nullptr || eg == nullptr || ex == nullptr) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(dy8) | reinterpret_cast<uintptr_t>(x8) | reinterpret_cast<uintptr_t>(dw) |
+       reinterpret_cast<uintptr_t>(ws)) % 16)
+    return hipErrorInvalidValue;
+  if (ldeg % 4 || ldex % 4 || ldeg < N || ldex < K ||
+      (reinterpret_cast<uintptr_t>(eg) | reinterpret_cast<uintptr_t>(ex)) % 4)
+    return hipErrorInvalidValue;
+  if (splits > 1 && ws == nullptr) return hipErrorInvalidValue;
+  const int64_t steps = (M + fp8::kWT - 1) / fp8::kWT;
+  fp8::XWArgs p;
+  p.g = static_cast<const uint8_t*>(dy8);
+  p.x = static_cast<const uint8_t*>(x8);
+  p.eg = static_cast<const uint8_t*>(eg);
+  p.ex = static_cast<const uint8_t*>(ex);
+  p.out = static_cast<uint16_t*>(dw);
+  p.ldg = ldg;
+  p.ldx = ldx;
+  p.ldeg = ldeg;
+  p.ldex = ldex;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.n_tiles = (int)((N + fp8::kT - 1) / fp8::kT);
+  p.k_tiles = (int)((K + fp8::kT - 1) / fp8::kT);
+  p.splits = (int)(splits < steps ? splits : steps);  // as madnn_fp8_wgrad
+  p.steps_per = (int)((steps + p.splits - 1) / p.splits);
+  p.splits = (int)((steps + p.steps_per - 1) / p.steps_per);
+  p.ws = p.splits > 1 ? ws : nullptr;
+  if ((int64_t)p.n_tiles * p.k_tiles * p.splits > 0x7fffffff) return hipErrorInvalidValue;
+  hipError_t e;
+  if (fmt_g == 0) e = fmt_x == 0 ? fp8::launch_mx_wgrad<0, 0>(p, stream) : fp8::launch_mx_wgrad<0, 1>(p, stream);
+  else e = fmt_x == 0 ? fp8::launch_mx_wgrad<1, 0>(p, stream) : fp8::launch_mx_wgrad<1, 1>(p, stream);
+  if (e != hipSuccess || p.splits == 1) return e;
+  const int64_t n = N * K;
+  hipLaunchKernelGGL(fp8::mx_wgrad_reduce_kernel, dim3((unsigned)stream_grid(n / 8, 256, 2048)), dim3(256), 0, stream,
+                     p.ws, p.out, p.splits, n);
   return hipGetLastError();
 }

@@ -424,36 +424,57 @@ def mx_dequantize(q: torch.Tensor, e: torch.Tensor, dtype=torch.float32) -> torc
     return q.to(dtype) * s
 
 
+def mx_quantize_columns(x: torch.Tensor, fmt: str = "e4m3"):
+    """``(qc, ec)``: the 2-D ``x`` [R, C] quantised in blocks of 32 ROWS per column, for a GEMM that reduces over
+    the rows (the weight gradient, K17XW): :func:`mx_quantize` of ``x.t()`` with the rows zero-padded to a multiple
+    of 32, transposed back and cut to ``R``.  ``qc`` [R, C], ``ec`` uint8 [ceil(R / 32), C]; any ``R``."""
+    r = x.shape[0]
+    qt, et = mx_quantize(torch.nn.functional.pad(x.detach(), (0, 0, 0, -r % MX_BLOCK)).t(), fmt)
+    return qt.t()[:r].contiguous(), et.t().contiguous()
+
+
+def mx_dequantize_columns(qc: torch.Tensor, ec: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """``qc[r, c] * 2^(ec[r // 32, c] - 127)`` in ``dtype``."""
+    return qc.to(dtype) * torch.exp2(ec.to(dtype) - 127).repeat_interleave(MX_BLOCK, 0)[:qc.shape[0]]
+
+
 class _LinearMx(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, residual):
+    def forward(ctx, x, w, b, residual, wgrad=False):
         acc = torch.float32 if x.dtype in (torch.bfloat16, torch.float16) else x.dtype
         y = mx_dequantize(*mx_quantize(x, "e4m3"), acc) @ mx_dequantize(*mx_quantize(w, "e4m3"), acc).t()
         if b is not None:
             y = y + b.to(acc)
         if residual is not None:
             y = y + residual.to(acc)
+        # with wgrad the backward sees the token-blocked e4m3 image of x, not x
+        xs = mx_dequantize_columns(*mx_quantize_columns(x.reshape(-1, x.shape[-1]), "e4m3"), acc) if wgrad else x
         # the data gradient reduces over out-features: W^T quantised anew in blocks along them
-        ctx.save_for_backward(x, mx_dequantize(*mx_quantize(w.t(), "e4m3"), acc))
-        ctx.meta = (acc, x.dtype, w.dtype, b.dtype if b is not None else None, residual is not None)
+        ctx.save_for_backward(xs, mx_dequantize(*mx_quantize(w.t(), "e4m3"), acc))
+        ctx.meta = (acc, x.dtype, w.dtype, b.dtype if b is not None else None, residual is not None, wgrad)
         return y.to(x.dtype)
 
     @staticmethod
     def backward(ctx, g):
         x, wtd = ctx.saved_tensors
-        acc, xdt, wdt, bdt, has_res = ctx.meta
+        acc, xdt, wdt, bdt, has_res, wgrad = ctx.meta
         dx = (mx_dequantize(*mx_quantize(g, "e4m3"), acc) @ wtd.t()).to(xdt)
         g2, x2 = g.reshape(-1, g.shape[-1]).to(acc), x.reshape(-1, x.shape[-1]).to(acc)
-        dw = (g2.t() @ x2).to(wdt)
+        gw = mx_dequantize_columns(*mx_quantize_columns(g.reshape(-1, g.shape[-1]), "e4m3"), acc) if wgrad else g2
+        dw = (gw.t() @ x2).to(wdt)
         db = g2.sum(0).to(bdt) if bdt is not None else None
-        return dx, dw, db, (g if has_res else None)
+        return dx, dw, db, (g if has_res else None), None
 
 
 def linear_mx(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
-              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+              residual: Optional[torch.Tensor] = None, wgrad: bool = False) -> torch.Tensor:
     """The MX FP8 Linear of ``ops.linear(fp8="mx")`` in plain torch, on any device and in any float dtype: the
     forward multiplies the dequantised block-scaled e4m3 images of ``x`` and ``w`` (blocks of 32 along
     in-features), adds bias and residual and rounds once; the data gradient multiplies the dequantised e4m3
     image of the output gradient with that of ``w`` RE-QUANTISED in blocks along out-features (its reduction);
-    weight, bias and residual gradients use the unquantised tensors.  Feature counts are multiples of 32."""
-    return _LinearMx.apply(x, w, b, residual)
+    weight, bias and residual gradients use the unquantised tensors -- or, with ``wgrad``
+    (``ops.linear(fp8="mx_wgrad")``, K17XW), the weight gradient multiplies the e4m3 images of the output gradient
+    and of ``x`` quantised a second time in blocks of 32 TOKENS per column (:func:`mx_quantize_columns`):
+    ``dW = dq(dy_c)^T @ dq(x_c)``, accumulated as the other products and rounded once.  Feature counts are
+    multiples of 32."""
+    return _LinearMx.apply(x, w, b, residual, wgrad)
